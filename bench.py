@@ -1,8 +1,22 @@
 """Benchmark: GPMDM particle-filter step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4,5}]
-                    [--rng {auto,philox,torch}] [--stream {mocap,predictive}] [--y-lambda L]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                    [--config {1,2,3,4,5}] [--rng {auto,philox,torch}]
+                    [--stream {mocap,predictive}] [--y-lambda L]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: it builds the model and the filter, runs W
+warm-up frames, times K frames and prints the line (the contract fields, ``ms_per_step``,
+``config``, ``roofline``, ``posterior_last``).  ``--full`` adds, after the timed frames,
+every other measurement and check listed below (``stages_ms_per_step``, ``nodedup``, ``ess_*``,
+``dyn_rows_last``, ``replay``, ``bank``, ``spread``, ``cutoff``, ``library_exchange``,
+``cpu_baseline``) with their own options; without ``--full`` those options are accepted and
+do nothing.  The timed loop, and so ``value`` and ``ms_per_step``, is the same either way.
+
+``--dump-outputs DIR`` writes what the caller of the timed step received in the last timed
+frame as float64 ``DIR/<name>.npy``: ``most_likely_class`` (1,), ``class_probabilities`` (C,)
+and ``current_state_mean`` (d,).  Model, observation stream and seeds are fixed, so the same
+arguments give the same inputs in every run and two builds can be compared array for array.
 
 ``--gpus N`` (N > 1) without a launcher around it starts N worker processes itself (one per
 GPU, RANK / LOCAL_RANK / WORLD_SIZE in their environment, before anything touches the GPU)
@@ -36,7 +50,8 @@ observation GP's output scales (exp(y_log_lambdas)); below 1 the likelihood is l
 Together they keep the cloud spread out (ESS well above the mocap stream's ~0.3%), so the
 resample path and the dynamics tiles are timed on many distinct ancestors.
 
-Prints ONE JSON line (rank 0) with the contract fields plus:
+Prints ONE JSON line (rank 0) with the contract fields plus (every field after ``roofline``
+only with ``--full``):
   roofline      dominant kernel (observation-GP tile kernel) vs the FP64 MFMA peak;
                 achieved = algorithmic FLOPs per launch (triangular form N(N+1) + 2N + 2ND
                 per particle; SURVEY §8(d)'s dense 2N^2 + 2ND is reported beside it) / mean
@@ -687,6 +702,14 @@ def library_exchange_line(new_filter, zs, steps, dist, device, P_total, warmup=3
                     "every rank"}
 
 
+def dump_outputs(path, arrays):
+    """``--dump-outputs DIR``: each array as DIR/<name>.npy (float64; a few hundred bytes in all)."""
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -898,6 +921,13 @@ def main():
     ap.add_argument("--steps", type=int, default=None,
                     help="timed frames (default: 500, configs[1]'s 500 frames; 20 for configs 3 and 5)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement and check (stage breakdown, "
+                         "nodedup, replay, bank, spread, cutoff, library exchange, CPU baseline); without it "
+                         "the run sets up, warms up, times --steps frames and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the read-outs of the last timed step (what the caller of the step receives) "
+                         "as DIR/<name>.npy, float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--config", type=int, default=2, choices=(1, 2, 3, 4, 5))
     ap.add_argument("--rng", default="auto", choices=("auto", "philox", "torch"),
@@ -989,9 +1019,10 @@ def main():
     P_total = WORKLOAD["P_per_gpu"] * world
     from gpmdm_amd import synthetic
     T = torch.from_numpy(synthetic.markov_matrix(WORKLOAD["C"]))
-    n_breakdown = min(args.steps, 10)
+    full = args.full
+    n_breakdown = min(args.steps, 10) if full else 0
     n_frames = args.warmup + args.steps + n_breakdown + 64
-    if args.config == 1:
+    if args.config == 1 and full:
         n_frames += args.steps          # the event-free pass of the notebook line
     comm = None
     if world > 1 and args.exchange == "library":
@@ -1066,17 +1097,26 @@ def main():
     elapsed = time.perf_counter() - t0
     pf.enable_timing(False)
     stages = pf.stage_times()
+    # what the caller of the timed step received in its last frame (the read-outs are cached
+    # on the host by the step's own calls: nothing runs on the GPU here)
+    outputs = {"most_likely_class": np.array([pf.get_most_likely_class()], dtype=np.float64),
+               "class_probabilities": pf.class_probabilities().numpy().astype(np.float64),
+               "current_state_mean": pf.current_state_mean().numpy().astype(np.float64)}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     # per-stage breakdown from a separate, untimed pass (every stage's events on)
-    pf.enable_timing(True)
     bd_rows = 0
-    for k in range(n_breakdown):            # the stream's next frames (no jump back in time)
-        one(args.warmup + args.steps + k)
-        bd_rows += pf.dynamics_rows()       # rows the dynamics GP evaluated this frame
-    torch.cuda.synchronize()
-    pf.enable_timing(False)
-    breakdown = pf.stage_times()
+    breakdown = None
+    if full:
+        pf.enable_timing(True)
+        for k in range(n_breakdown):            # the stream's next frames (no jump back in time)
+            one(args.warmup + args.steps + k)
+            bd_rows += pf.dynamics_rows()       # rows the dynamics GP evaluated this frame
+        torch.cuda.synchronize()
+        pf.enable_timing(False)
+        breakdown = pf.stage_times()
     untimed_ms = None
-    if args.config == 1 and world == 1:
+    if full and args.config == 1 and world == 1:
         # the same loop once more without the roofline's two timing events per frame (at
         # 0.1 ms per frame their records are a visible part of the frame)
         k0 = args.warmup + args.steps + n_breakdown
@@ -1093,19 +1133,22 @@ def main():
     post = pf.class_probabilities().numpy()
     if stream_check is not None:     # the timed filter followed the stream's own trajectory
         stream_check["replay_matches"] = bool(np.array_equal(post, stream_check.pop("posterior")))
-    dyn_rows = pf.dynamics_rows()
-    w_last = pf.export_state()["w"]
-    ess = float(1.0 / np.sum(w_last * w_last))
-    bank = bank_line(model, T, args.bank, P_total, zs, args.warmup, args.steps) if args.bank and world == 1 else None
-    nodedup = None if args.no_nodedup else nodedup_line(model, T, P_total, group, dist, device, zs, args.steps, rng,
+    dyn_rows = ess = None
+    if full:
+        dyn_rows = pf.dynamics_rows()
+        w_last = pf.export_state()["w"]
+        ess = float(1.0 / np.sum(w_last * w_last))
+    bank = (bank_line(model, T, args.bank, P_total, zs, args.warmup, args.steps)
+            if full and args.bank and world == 1 else None)
+    nodedup = None if (args.no_nodedup or not full) else nodedup_line(model, T, P_total, group, dist, device, zs, args.steps, rng,
                                                                 args.dyn_tiles)
     rep = None
     if args.replay_steps is None:
         args.replay_steps = 30 if (args.config == 2 and rng == "philox" and args.stream == "mocap") else 0
-    if args.replay_steps and world == 1:
+    if full and args.replay_steps and world == 1:
         rep = replay_line(model, T, P_total, zs, 3, args.replay_steps, elapsed / args.steps * 1e3)
     libx = None
-    if world > 1 and backend == "nccl" and args.library_steps > 0:
+    if full and world > 1 and backend == "nccl" and args.library_steps > 0:
         if comm is None:
             try:
                 comm = library_comm(world, rank, local, group, device)
@@ -1127,7 +1170,7 @@ def main():
     if args.spread_steps is None:
         args.spread_steps = 30 if (args.config == 2 and args.stream == "mocap" and args.y_lambda == 1.0) else 0
     spread = (spread_line(device, args.spread_steps, y_lambda=args.spread_lambda, dyn_tiles=args.dyn_tiles)
-              if args.spread_steps and world == 1 else None)
+              if full and args.spread_steps and world == 1 else None)
     N, D, d = model.X.shape[0], model.D, model.d
     P_local = P_total // world
     alg, dense, executed = obs_kernel_flops(N, D)
@@ -1136,7 +1179,7 @@ def main():
     if args.cutoff_steps is None:
         args.cutoff_steps = 20 if (args.config in (2, 3, 5) and rng == "philox" and args.stream == "mocap") else 0
     cut = None
-    if args.cutoff_steps and world == 1 and len(zs) >= args.warmup + args.cutoff_steps + 10:
+    if full and args.cutoff_steps and world == 1 and len(zs) >= args.warmup + args.cutoff_steps + 10:
         try:   # reported beside the headline, never in place of it
             cut = cutoff_line(model, T, P_total, zs, args.warmup, args.cutoff_steps, elapsed / args.steps * 1e3,
                               obs_launch_s * 1e3, split=args.cutoff_split)
@@ -1161,6 +1204,7 @@ def main():
         "rehearsal": bool(world > ndev),
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": full,
         "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
@@ -1196,20 +1240,24 @@ def main():
                      "dense_form_equivalent_tflops": dense * P_local / obs_launch_s / 1e12,
                      "launch_ms": obs_launch_s * 1e3,
                      "timed_launches": obs_n, "events_every_nth_frame": sample},
-        "stages_ms_per_step": {k: v[0] / max(v[1], 1) for k, v in breakdown.items()},
-        "nodedup": nodedup,
-        "ess_last": ess,
         "stream_check": stream_check,
-        "ess_frac_last": ess / P_total,
         "posterior_last": [float(x) for x in post],
-        "dyn_rows_last": {"evaluated": dyn_rows, "particles": P_local,
-                          "breakdown_mean": bd_rows / max(n_breakdown, 1),
-                          "dyn_gemm_tflops": dyn_row_flops(model) * bd_rows
-                          / max(breakdown["dyn_gemm"][0], 1e-9) / 1e9,
-                          "note": "dynamics GP rows: one per distinct (ancestor, class) key (bitwise-"
-                                  "identical ancestor de-duplication, DESIGN.md §3); breakdown_mean and "
-                                  "dyn_gemm_tflops over the stage-breakdown pass"},
     }
+    if args.dump_outputs:
+        rec["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": {k: list(v.shape) for k, v in outputs.items()}}
+    if full:
+        rec.update({
+            "stages_ms_per_step": {k: v[0] / max(v[1], 1) for k, v in breakdown.items()},
+            "nodedup": nodedup,
+            "ess_last": ess,
+            "ess_frac_last": ess / P_total,
+            "dyn_rows_last": {"evaluated": dyn_rows, "particles": P_local,
+                              "breakdown_mean": bd_rows / max(n_breakdown, 1),
+                              "dyn_gemm_tflops": dyn_row_flops(model) * bd_rows
+                              / max(breakdown["dyn_gemm"][0], 1e-9) / 1e9,
+                              "note": "dynamics GP rows: one per distinct (ancestor, class) key (bitwise-"
+                                      "identical ancestor de-duplication, DESIGN.md §3); breakdown_mean and "
+                                      "dyn_gemm_tflops over the stage-breakdown pass"}})
     if libx is not None:
         rec["library_exchange"] = libx
     if rep is not None:
@@ -1227,10 +1275,11 @@ def main():
             "published": 78.2, "published_source": "test_gpmdm_pf.ipynb:259-260 (12.78 FPS, author's laptop CPU)",
             "container": 16.3, "container_source": "BASELINE.md §2 (unmodified reference, 8 cores, N=500, P=100)",
             "speedup_vs_published": 78.2 / ms, "speedup_vs_container": 16.3 / ms}
-        rec["ms_per_frame_without_timing_events"] = {
-            "value": untimed_ms, "note": "the next frames of the stream, same loop, no stage events "
-                                         "(ms_per_step keeps the roofline kernel's two events per frame)"}
-    if rank == 0 and not args.no_cpu_baseline:
+        if full:
+            rec["ms_per_frame_without_timing_events"] = {
+                "value": untimed_ms, "note": "the next frames of the stream, same loop, no stage events "
+                                             "(ms_per_step keeps the roofline kernel's two events per frame)"}
+    if full and rank == 0 and not args.no_cpu_baseline:
         # after every timed pass (the other ranks wait at the barrier below); at N > 1 the
         # same per-GPU workload, so the N-GPU line carries the CPU baseline beside its value
         try:

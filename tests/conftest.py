@@ -14,7 +14,13 @@ def pytest_configure(config):
 
 
 def load_fixture(name):
-    return dict(np.load(GOLDEN / f"{name}.npz", allow_pickle=False))
+    """The fixture's arrays: <name>.npz and, for a fixture too large for one committed file
+    (1 MiB), its <name>.partK.npz files (golden/make_golden.py's save splits by array)."""
+    out = {}
+    for p in [GOLDEN / f"{name}.npz", *sorted(GOLDEN.glob(f"{name}.part*.npz"))]:
+        with np.load(p, allow_pickle=False) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def seq_lengths(f):

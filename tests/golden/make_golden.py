@@ -170,10 +170,34 @@ def run_filter(m, T, P, frames, z, seed, record_from=0):
     return out
 
 
+PART_BYTES = 960 * 1024   # no committed file above 1 MiB: a larger fixture is split by array
+
+
+def split_arrays(arrays):
+    """The arrays in order, packed first-fit into groups whose compressed size stays below
+    PART_BYTES (conftest.load_fixture reads <name>.npz and every <name>.partK.npz)."""
+    import io
+    groups, sizes = [], []
+    for k, v in arrays.items():
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **{k: v})
+        n = buf.getbuffer().nbytes
+        for g, _ in enumerate(groups):
+            if sizes[g] + n <= PART_BYTES:
+                groups[g][k] = v
+                sizes[g] += n
+                break
+        else:
+            groups.append({k: v})
+            sizes.append(n)
+    return groups
+
+
 def save(name, arrays):
-    path = OUT / name
-    np.savez_compressed(path, **arrays)
-    print(f"wrote {path} ({path.stat().st_size / 1e6:.2f} MB)")
+    for g, part in enumerate(split_arrays(arrays)):
+        path = OUT / (name if g == 0 else name.replace(".npz", f".part{g + 1}.npz"))
+        np.savez_compressed(path, **part)
+        print(f"wrote {path} ({path.stat().st_size / 1e6:.2f} MB)")
 
 
 def main():

@@ -13,7 +13,7 @@ if [ "$1" = prepare ]; then
   exit 0
 fi
 out=${2:-gpurun_out/ab_lib}; rounds=${3:-2}; shift 3 2>/dev/null
-args=${*:---steps 300 --no-cpu-baseline --spread-steps 0 --no-nodedup}
+args=${*:---full --steps 300 --no-cpu-baseline --spread-steps 0 --no-nodedup}
 mkdir -p "$out"
 for r in $(seq "$rounds"); do
   for v in new prev; do

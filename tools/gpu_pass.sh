@@ -48,18 +48,18 @@ check)
       || { echo "smoke failed rc=$?"; tail -20 $out/smoke.log; exit 1; }
     tail -1 $out/smoke.log
   fi
-  timeout -k 10 400 python -u bench.py > $out/bench.json 2> $out/bench.err \
+  timeout -k 10 400 python -u bench.py --full > $out/bench.json 2> $out/bench.err \
     || { echo "bench failed rc=$?"; tail -20 $out/bench.err; exit 1; }
   show $out/bench.json bench
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -- python bench.py --steps 100 --warmup 5 $HEAD_ARGS > $out/kt.log 2>&1 \
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -- python bench.py --full --steps 100 --warmup 5 $HEAD_ARGS > $out/kt.log 2>&1 \
     || { echo "kernel trace failed rc=$?"; tail -20 $out/kt.log; exit 1; }
   python tools/headline_trace.py $out/kt --steps 100 --warmup 5 --commit "$commit" \
-    --command "rocprofv3 --kernel-trace --stats -- python bench.py --steps 100 --warmup 5 $HEAD_ARGS" --out $out/headline_obs.json
+    --command "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 100 --warmup 5 $HEAD_ARGS" --out $out/headline_obs.json
   if [ "$ab" = ab ]; then
     for r in 1 2 3; do
       for v in new prev; do
         dir=.; [ $v = prev ] && dir=tools/ab_prev
-        (cd $dir && timeout -k 10 240 python -u bench.py --steps 300 $HEAD_ARGS) > $out/ab_${v}_$r.json 2> $out/ab_${v}_$r.err \
+        (cd $dir && timeout -k 10 240 python -u bench.py --full --steps 300 $HEAD_ARGS) > $out/ab_${v}_$r.json 2> $out/ab_${v}_$r.err \
           || { echo "ab $v failed"; tail -5 $out/ab_${v}_$r.err; exit 1; }
         show $out/ab_${v}_$r.json "headline $v"
         (cd $dir && timeout -k 10 240 python -u bench.py --config 1 --no-cpu-baseline --bank 0) > $out/c1_${v}_$r.json 2> $out/c1_${v}_$r.err \
@@ -79,9 +79,9 @@ check)
 cutoff)
   for c in ${*:-2 3 5}; do
     case $c in
-      2) args="--steps 100 $HEAD_ARGS"; lim=400 ;;
-      3) args="--config 3 --steps 10 --no-cpu-baseline --no-nodedup --cutoff-steps 10"; lim=600 ;;
-      5) args="--config 5 --steps 5 --warmup 2 --no-cpu-baseline --no-nodedup --cutoff-steps 5"; lim=900 ;;
+      2) args="--full --steps 100 $HEAD_ARGS"; lim=400 ;;
+      3) args="--full --config 3 --steps 10 --no-cpu-baseline --no-nodedup --cutoff-steps 10"; lim=600 ;;
+      5) args="--full --config 5 --steps 5 --warmup 2 --no-cpu-baseline --no-nodedup --cutoff-steps 5"; lim=900 ;;
     esac
     timeout -k 10 $lim python -u bench.py $args > $out/c$c.json 2> $out/c$c.err \
       || { echo "config $c failed rc=$?"; tail -5 $out/c$c.err; exit 1; }
@@ -118,17 +118,17 @@ cutoff-ab)
     done
     for v in new prev; do
       dir=.; [ $v = prev ] && dir=tools/ab_prev
-      (cd $dir && timeout -k 10 300 python -u bench.py --steps 40 --cutoff-steps 20 $HEAD_ARGS) > $out/c2_${v}_$r.json 2> $out/c2_${v}_$r.err \
+      (cd $dir && timeout -k 10 300 python -u bench.py --full --steps 40 --cutoff-steps 20 $HEAD_ARGS) > $out/c2_${v}_$r.json 2> $out/c2_${v}_$r.err \
         || { echo "c2 $v failed"; tail -5 $out/c2_${v}_$r.err; exit 1; }
       show $out/c2_${v}_$r.json "c2 $v r$r"
     done
   done
   ;;
 cutoff-pmc)
-  BENCH_ARGS="--spread-steps 0 --replay-steps 0 --no-nodedup --cutoff-steps 2" bash tools/pmc_passes.sh $out/pmc "FETCH_SIZE" "WRITE_SIZE" \
+  BENCH_ARGS="--full --spread-steps 0 --replay-steps 0 --no-nodedup --cutoff-steps 2" bash tools/pmc_passes.sh $out/pmc "FETCH_SIZE" "WRITE_SIZE" \
     "$COUNTERS_A" "$COUNTERS_B" || exit 1
   python tools/pmc_summary.py $out/pmc --commit "$commit" \
-    --command "bench.py --steps 2 --warmup 1 --no-cpu-baseline --spread-steps 0 --replay-steps 0 --no-nodedup --cutoff-steps 2" \
+    --command "bench.py --steps 2 --warmup 1 --no-cpu-baseline --full --spread-steps 0 --replay-steps 0 --no-nodedup --cutoff-steps 2" \
     --out $out/pmc_summary.json > $out/pmc_summary.txt 2>&1 || { echo "pmc summary failed"; exit 1; }
   ;;
 spread-split)
@@ -156,7 +156,7 @@ spread-pmc)
   ;;
 configs)
   for c in ${*:-3 4 5}; do
-    timeout -k 10 600 python -u bench.py --config $c > $out/c$c.json 2> $out/c$c.err || { echo "config $c failed"; tail -5 $out/c$c.err; exit 1; }
+    timeout -k 10 600 python -u bench.py --full --config $c > $out/c$c.json 2> $out/c$c.err || { echo "config $c failed"; tail -5 $out/c$c.err; exit 1; }
     python -c "import json;d=json.load(open('$out/c$c.json'));cb=d.get('cpu_baseline') or {};print('config $c', round(d['ms_per_step'],2), 'ms/step', '%.4g' % d['value'], 'frac', round(d['roofline']['frac'],3), 'cpu', cb.get('value'), cb.get('cores'))"
   done
   ;;

@@ -1,6 +1,6 @@
 """Headline-only kernel-trace summary: the observation-tile launches of bench.py's timed loop.
 
-    rocprofv3 --kernel-trace --output-format csv -d <dir> -- python bench.py --steps K --warmup W \
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -- python bench.py --full --steps K --warmup W \
         --no-cpu-baseline --spread-steps 0 --replay-steps 0 --no-nodedup
     python tools/headline_trace.py <dir> --steps K --warmup W [--out profiles/rNN/headline_obs.json]
 
