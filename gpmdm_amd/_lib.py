@@ -91,6 +91,8 @@ _SIGS = {
     "gpmdm_pf_obs_cutoff_auto": (c_int, [c_void_p, POINTER(c_int), POINTER(ctypes.c_double)]),
     "gpmdm_pf_obs_cutoff_stats": (c_int, [c_void_p, _i64p, _i64p, c_int, c_void_p]),
     "gpmdm_pf_predict": (c_int, [c_void_p, _dp, c_void_p]),
+    "gpmdm_pf_set_obs_mask": (c_int, [c_void_p, c_void_p]),
+    "gpmdm_pf_observation": (c_int, [c_void_p, _dp, _dp, c_void_p]),
     "gpmdm_pf_set_comm": (c_int, [c_void_p, c_void_p, c_int]),
     "gpmdm_comm_unique_id": (c_int, [c_void_p]),
     "gpmdm_comm_init": (c_int, [c_int, c_int, c_void_p, c_int, POINTER(c_void_p)]),

@@ -409,6 +409,8 @@ int gpmdm_pf_propagate_multi(gpmdm_pf_t* pfs, int n, const double* zh, const dou
     CHECK(pf->comm, "gpmdm_pf_propagate_multi needs every filter's communicator (gpmdm_pf_set_comm)");
     CHECK(pf->comm_loop == pfs[0]->comm_loop, "gpmdm_pf_propagate_multi: every filter's communicator of one kind");
     CHECK(pf->n_ranks == n && pf->rank == i, "filter i must be rank i of n");
+    CHECK(pf->obs_mask == pfs[0]->obs_mask, "gpmdm_pf_propagate_multi: the filters' observation masks differ "
+                                            "(gpmdm_pf_set_obs_mask on every rank)");
     if (!pf->switched || pf->preswitched) return fail(GPMDM_E_STATE, "propagate called before switch");
     if (pf->rng_mode == GPMDM_RNG_REPLAY) CHECK(normals, "replay mode needs the dynamics normals");
   }

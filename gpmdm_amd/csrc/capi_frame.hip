@@ -399,7 +399,7 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
     pf->zslot ^= 1;
   } else {
     HIPCHK(pf->zslot_free());
-    std::memcpy(pf->zpin[zk], zh, sizeof(double) * D * pf->F);
+    pf->stage_z(pf->zpin[zk], zh);
     if (zmap)
       zsrc = pf->zdev[zk];
     else
@@ -407,7 +407,18 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
     pf->zslot ^= 1;
   }
   const long long nl = pf->nloc;
-  if (nl > 0) {
+  // a masked frame (gpmdm_pf_set_obs_mask): the same launches on the observed dimensions
+  const bool masked = pf->masked();
+  const double* lam2 = masked ? pf->lam2_obs : m->y_lam2_dev;
+  if (masked && pf->D_obs == 0) {
+    // sensor blackout: a pure prediction step.  No observation kernel runs; ll is exactly 0
+    // for every particle (the other ranks' entries arrive with the exchange as the same 0),
+    // so the normaliser's weights are exactly 1/P.
+    HIPCHK(hipMemsetAsync(pf->ll, 0, sizeof(double) * pf->P, s));
+    pf->cut_frame = pf->cut_frame_auto = false;
+    pf->ll_pending = false;
+    pf->bmax_ready = false;
+  } else if (nl > 0) {
     // ---- observation GP + likelihood over particles [lo, hi) ----
     pf->mark_begin(s, GPMDM_STAGE_OBS_GEMM, t0);
     // the opt-in kernel-value cutoff: its own kernel over the cutoff image (obs_cutoff.h),
@@ -468,7 +479,7 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
       cp.q = pf->qobs;
       cp.S = pf->sobs;
       cp.z = zsrc;
-      cp.lam2 = m->y_lam2_dev;
+      cp.lam2 = lam2;
       cp.Pf = pf->Pf;
       cp.sp_stats = auto_frame ? pf->cut_auto_dev : (pf->sp_stats_on ? pf->sp_stats : nullptr);
       // the grid's tail: equal workgroups run in whole rounds of the resident slots, so the
@@ -519,7 +530,7 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
       tp.ld_q = nl;
       tp.spart = pf->sobs;
       tp.z = zsrc;
-      tp.lam2 = m->y_lam2_dev;
+      tp.lam2 = lam2;
       tp.Pf = pf->Pf;
       launch_gp_tile(tp, d, false, s);
     }
@@ -539,6 +550,11 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
     oa.Pf = pf->Pf;
     oa.il2 = m->y_il2_dev;
     oa.ll_const = (double)((float)(0.5 * D) * (float)1.8378770351409912);
+    if (masked) {
+      oa.D = pf->D_obs;
+      oa.sum_log_il2 = pf->sum_log_il2_obs;
+      oa.ll_const = pf->ll_const_obs;
+    }
     oa.ll = pf->ll;
     oa.ll_offset = obs_lo;
     oa.own = obs_order;
@@ -618,7 +634,7 @@ int gpmdm_pf_propagate(gpmdm_pf_t pf, const double* zh, const double* normals, v
   const bool zstage = pf->nloc > 4096 && pf->nloc >= (long long)D * pf->F;
   if (zstage) {
     HIPCHK(pf->zslot_free());
-    std::memcpy(pf->zpin[pf->zslot], zh, sizeof(double) * D * pf->F);
+    pf->stage_z(pf->zpin[pf->zslot], zh);
   }
   const int rc = propagate_dynamics(pf, normals, (hipStream_t)stream, zstage);
   if (rc) {

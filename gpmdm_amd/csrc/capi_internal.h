@@ -28,6 +28,7 @@
 #include "../../include/gpmdm_hip.h"
 #include "common.h"
 #include "host_image.h"
+#include "obs_readout.h"
 #include "pf_kernels.h"
 #include "status.h"
 
@@ -120,6 +121,10 @@ struct gpmdm_model {
   double* y_il2_dev = nullptr;
   double* y_lam2_dev = nullptr;   // 1 / il2 = exp(y_log_lambdas)^2
   double sum_log_il2 = 0.0;
+  // the filtered-pose read-out (obs_readout.h): beta = K_y^-1 Y in its own fragment order,
+  // and the observation kernel's lengthscales on the device
+  double* ro_beta = nullptr;
+  double* y_ls_dev = nullptr;
   // Observation-GP cutoff image (gpmdm_model_set_obs_cutoff; empty: not set): K^-1's block
   // upper triangle and M over the training rows in a spatial order, tile-major
   // (host_image.h CutoffPacker, obs_cutoff.h), the K-step spheres, and the cutoff (tau; cut2 =
@@ -182,6 +187,8 @@ struct gpmdm_model {
     release_cutoff();
     dfree(y_il2_dev);
     dfree(y_lam2_dev);
+    dfree(ro_beta);
+    dfree(y_ls_dev);
   }
 };
 
@@ -290,6 +297,32 @@ struct gpmdm_pf {
     }
     return GPMDM_OK;
   }
+  // Masked observations (gpmdm_pf_set_obs_mask; obs_mask empty: every dimension observed).
+  // The observation kernels reduce S = sum_j (z_j - mu_j)^2 lam2_j against a lam2 pointer and
+  // the finish takes D, sum_j log il2_j and the constant as arguments, so a masked frame is
+  // the same launches with lam2_obs (lam2_j where observed, exactly 0 elsewhere) and the three
+  // scalars of the observed dimensions -- the likelihood of the model restricted to them.
+  // z is zeroed at the unobserved positions in the staging copies (stage_z), so a NaN there
+  // never reaches a kernel.
+  std::vector<unsigned char> obs_mask;
+  double* lam2_obs = nullptr;
+  int D_obs = 0;
+  double sum_log_il2_obs = 0.0, ll_const_obs = 0.0;
+  bool masked() const { return !obs_mask.empty(); }
+  void stage_z(double* dst, const double* zh) const {   // single filters only when masked
+    const int D = m->D;
+    if (!masked()) {
+      std::memcpy(dst, zh, sizeof(double) * D * F);
+      return;
+    }
+    for (int j = 0; j < D; ++j) dst[j] = obs_mask[(size_t)j] ? zh[j] : 0.0;
+  }
+  // The filtered-pose read-out (gpmdm_pf_observation, obs_readout.h): the tiles' partials,
+  // the device result {mean, spread} and its pinned landing buffer, allocated on first use;
+  // ro_obs_ev follows the last read-out's launches (quiesce waits for it).
+  double *ro_part = nullptr, *ro_obs = nullptr, *ro_obs_pin = nullptr;
+  hipEvent_t ro_obs_ev = nullptr;
+  bool ro_obs_pending = false;
   // likelihood finish deferred into the resampling launch (single-shard small filters:
   // k_small_resample computes ll first, one launch less per frame); flush_ll runs it for
   // any reader of ll that comes first
@@ -605,6 +638,11 @@ struct gpmdm_pf {
     hfree(cut_auto_host);
     dfree(cut_part);
     dfree(cut_split);
+    dfree(lam2_obs);
+    dfree(ro_part);
+    dfree(ro_obs);
+    hfree(ro_obs_pin);
+    if (ro_obs_ev) (void)hipEventDestroy(ro_obs_ev);
     dfree(bmax);
     dfree(bmax_rows);
     dfree(owner);

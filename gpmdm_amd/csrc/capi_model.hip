@@ -251,6 +251,14 @@ int gpmdm_model_create(const gpmdm_model_desc* desc, int device, gpmdm_model_t* 
       return fail(GPMDM_E_HIP, "upload lambda^2");
     }
   }
+  {
+    // the filtered-pose read-out's operands (obs_readout.h)
+    std::vector<double> bro;
+    pack_readout_beta(desc->obs_beta, m->N, m->D, bro);
+    rc = upload(&m->ro_beta, bro);
+    if (!rc) rc = upload(&m->y_ls_dev, m->y_ls);
+    if (rc) { delete m; return rc; }
+  }
   *out = m;
   return GPMDM_OK;
 }

@@ -300,6 +300,36 @@ int quiesce(gpmdm_pf* pf) {
   }
   if (pf->up_stream) HIPCHK(hipStreamSynchronize(pf->up_stream));
   if (pf->cstream) HIPCHK(hipStreamSynchronize(pf->cstream));
+  if (pf->ro_obs_pending) {            // a filtered-pose read-out launched without a copy
+    HIPCHK(hipEventSynchronize(pf->ro_obs_ev));
+    pf->ro_obs_pending = false;
+  }
+  return GPMDM_OK;
+}
+
+// The mask's device array and scalars from the filter's current model (gpmdm_pf_set_obs_mask,
+// and again when the filter is rebound to a rebuilt model).  Between frames.
+static int install_obs_mask(gpmdm_pf* pf, const std::vector<unsigned char>& mask) {
+  const gpmdm_model* m = pf->m;
+  const int D = m->D;
+  // the last frame's observation kernels may still read lam2_obs: they precede its read-out
+  // (a pending pre-switch reads neither, and stays pending)
+  HIPCHK(pf->zslot_free());
+  if (!pf->lam2_obs) TRY(dalloc(&pf->lam2_obs, (size_t)D));
+  std::vector<double> lam2((size_t)D, 0.0);
+  int n_obs = 0;
+  double sl = 0.0;
+  for (int j = 0; j < D; ++j)
+    if (mask[(size_t)j]) {
+      lam2[(size_t)j] = 1.0 / m->y_il2[(size_t)j];   // the model's y_lam2_dev value
+      sl += std::log(m->y_il2[(size_t)j]);
+      ++n_obs;
+    }
+  TRY(h2d(pf->lam2_obs, lam2.data(), sizeof(double) * D));
+  pf->obs_mask = mask;
+  pf->D_obs = n_obs;
+  pf->sum_log_il2_obs = sl;
+  pf->ll_const_obs = (double)((float)(0.5 * n_obs) * (float)1.8378770351409912);   // capi_frame.hip weigh()
   return GPMDM_OK;
 }
 
@@ -619,6 +649,10 @@ int gpmdm_pf_set_model(gpmdm_pf_t pf, gpmdm_model_t m) {
   m->add_user(pf);
   pf->m = m;
   model_release(old);
+  if (pf->masked()) {                  // the mask's lambda^2 and scalars are the new model's
+    const std::vector<unsigned char> mask = pf->obs_mask;
+    TRY(install_obs_mask(pf, mask));
+  }
   return GPMDM_OK;
 }
 
@@ -661,6 +695,64 @@ int gpmdm_pf_set_obs_cutoff(gpmdm_pf_t pf, int mode) {
   pf->cut_auto = mode == 3;
   pf->cut_auto_pending = false;        // (a fresh measurement: the next frame probes)
   pf->cut_auto_frac = -1.0;
+  return GPMDM_OK;
+}
+
+int gpmdm_pf_set_obs_mask(gpmdm_pf_t pf, const uint8_t* observed) {
+  CHECK(pf, "null handle");
+  CHECK(pf->F == 1, "filter banks share one lam2 across the filters of a tile: no observation mask "
+                    "(per-filter masks are not supported)");
+  if ((pf->switched && !pf->preswitched) || pf->dyn_done || pf->propagated)
+    return fail(GPMDM_E_STATE, "set_obs_mask between switch and resample");
+  gpmdm_model* m = pf->m;
+  const int D = m->D;
+  if (!observed) {
+    pf->obs_mask.clear();              // (lam2_obs is kept for the next mask)
+    return GPMDM_OK;
+  }
+  HIPCHK(hipSetDevice(m->device));
+  std::vector<unsigned char> mask((size_t)D);
+  for (int j = 0; j < D; ++j) mask[(size_t)j] = observed[j] ? 1 : 0;
+  return install_obs_mask(pf, mask);
+}
+
+int gpmdm_pf_observation(gpmdm_pf_t pf, double* mean, double* spread, void* stream) {
+  CHECK(pf, "null handle");
+  CHECK(pf->F == 1, "the filtered-pose read-out serves single filters, not banks");
+  if (!pf->initialised) return fail(GPMDM_E_STATE, "particle filter not initialised");
+  gpmdm_model* m = pf->m;
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int D = m->D;
+  if (!pf->ro_part) TRY(dalloc(&pf->ro_part, readout_part_doubles(pf->P, D)));
+  if (!pf->ro_obs) TRY(dalloc(&pf->ro_obs, (size_t)2 * D));
+  if (!pf->ro_obs_pin) TRY(halloc(&pf->ro_obs_pin, (size_t)2 * D, 0));
+  if (!pf->ro_obs_ev) HIPCHK(hipEventCreateWithFlags(&pf->ro_obs_ev, hipEventDisableTiming));
+  // the particles the filter holds now (X: written by the resample only; a pending pre-switch
+  // reads it too and stays pending)
+  ReadoutParams rp{};
+  rp.X = pf->X;
+  rp.P = pf->P;
+  rp.d = m->d;
+  rp.D = D;
+  rp.ls = m->y_ls_dev;
+  rp.Xrec = m->obs.Xrec;
+  rp.nks = ksteps((int)m->N);
+  rp.Bro = m->ro_beta;
+  rp.n_groups = readout_groups(D);
+  rp.part = pf->ro_part;
+  rp.out = pf->ro_obs;
+  launch_obs_readout(rp, s);
+  HIPCHK(hipGetLastError());
+  if (!mean && !spread) {              // launched only (timing): the handle's lifecycle waits for it
+    HIPCHK(hipEventRecord(pf->ro_obs_ev, s));
+    pf->ro_obs_pending = true;
+    return GPMDM_OK;
+  }
+  HIPCHK(hipMemcpyAsync(pf->ro_obs_pin, pf->ro_obs, sizeof(double) * 2 * D, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (mean) std::memcpy(mean, pf->ro_obs_pin, sizeof(double) * D);
+  if (spread) std::memcpy(spread, pf->ro_obs_pin + D, sizeof(double) * D);
   return GPMDM_OK;
 }
 

@@ -286,12 +286,45 @@ class GPMDM_PF:
     def reset(self):
         self._init_particles()
 
-    def update(self, z):
-        """gpmdm_pf.py:117-135: switch classes, propagate dynamics, weight, resample."""
+    def _check_mask(self, observed):
+        """``observed`` as D uint8 flags (None: every dimension observed); shape errors are
+        raised here, before the library is touched."""
+        if observed is None:
+            return None
+        m = np.asarray(observed, dtype=bool).reshape(-1)
+        if m.shape[0] != self.observation_dim:
+            raise ValueError(f"observed must have {self.observation_dim} flags, got {m.shape[0]}")
+        return np.ascontiguousarray(m, dtype=np.uint8)
+
+    def _set_mask(self, mask):
+        """Put the mask (``_check_mask``'s result) in force on every handle this process
+        drives, if it differs from the one in force (gpmdm_pf_set_obs_mask)."""
+        key = None if mask is None else mask.tobytes()
+        if key == getattr(self, "_mask_key", None):
+            return
+        lib = _lib.load()
+        ptr = None if mask is None else ctypes.c_void_p(mask.ctypes.data)
+        for h in [self._h] + [p[0] for p in self._peers]:
+            _lib.check(lib.gpmdm_pf_set_obs_mask(h, ptr), "observed")
+        self._mask_key = key
+
+    def update(self, z, observed=None):
+        """gpmdm_pf.py:117-135: switch classes, propagate dynamics, weight, resample.
+
+        ``observed`` (anything ``np.asarray(..., bool)`` turns into D flags; default: all):
+        the dimensions of ``z`` that were seen this frame.  The particles are weighted by the
+        reference's likelihood on the model restricted to those dimensions; ``z`` at the
+        others is ignored (it may be NaN).  For a capture stream that marks a dropped marker
+        with NaN the idiom is ``pf.update(z, observed=np.isfinite(z))``.  With no dimension
+        observed the frame is a pure prediction step (``w`` exactly 1/P).  ``update(z)``
+        without the argument is the reference's update, NaN propagation included.
+        ``current_observation()`` then reads the pose back, missing joints imputed."""
         z = _as_f64_vector(z)
         if z.shape[0] != self.observation_dim:
             raise ValueError(f"observation must have {self.observation_dim} values, got {z.shape[0]}")
+        mask = self._check_mask(observed)
         self._sync_model()
+        self._set_mask(mask)
         lib, h, s = _lib.load(), self._h, self._stream()
         P, C, d = self._num_particles, self.num_classes, self.latent_dim
         if self._rng == "torch":
@@ -356,14 +389,19 @@ class GPMDM_PF:
         return (isinstance(self._draws, replay.ParallelFrameDraws) and not self._peers and self._world == 1
                 and not os.environ.get("GPMDM_NO_PRESWITCH"))
 
-    def update_with_draws(self, z, exp_draws, normals, uniforms):
+    def update_with_draws(self, z, exp_draws, normals, uniforms, observed=None):
         """One update with explicit random draws in the reference's order (replay: see
         gpmdm_amd.replay): exp_draws P x C, normals (sum_c P_c) x d grouped by class,
-        uniforms P (multinomial) or 1 (systematic).  Requires rng='torch'."""
+        uniforms P (multinomial) or 1 (systematic).  Requires rng='torch'.  ``observed``:
+        as in ``update``."""
         if self._rng != "torch":
             raise ValueError("explicit draws need rng='torch' (replay mode)")
         z = _as_f64_vector(z)
+        if z.shape[0] != self.observation_dim:
+            raise ValueError(f"observation must have {self.observation_dim} values, got {z.shape[0]}")
+        mask = self._check_mask(observed)
         self._sync_model()
+        self._set_mask(mask)
         lib, h, s = _lib.load(), self._h, self._stream()
         P, C, d = self._num_particles, self.num_classes, self.latent_dim
         E = np.ascontiguousarray(exp_draws, dtype=np.float64).reshape(P, C)
@@ -471,6 +509,30 @@ class GPMDM_PF:
         out = np.zeros(self.latent_dim)
         _lib.check(_lib.load().gpmdm_pf_predict(self._h, _lib.dptr(out), self._stream()), "predict")
         return torch.from_numpy(out)
+
+    def current_observation(self, spread: bool = True):
+        """The filtered pose: the observation GP's mean (gpmdm.py:955-957) averaged over the
+        particles the filter holds now, ``mean[j] = (1/P) sum_p mu_j(x_p)`` -- the denoised
+        joint angles, and after masked updates the imputed values of the joints that were not
+        seen -- and with ``spread`` the cloud's variance of each, ``(1/P) sum_p (mu_j(x_p) -
+        mean[j])^2`` (the particles' disagreement, not the GP's own noise variance).  Computed
+        on the device by a mean-only GP tile (gpmdm_pf_observation); does not change the
+        filter state and draws no random numbers; the same cloud gives bitwise the same
+        values.  A sharded filter evaluates its replicated cloud on rank 0."""
+        self._sync_model()
+        D = self.observation_dim
+        mean = np.zeros(D)
+        var = np.zeros(D) if spread else None
+        _lib.check(_lib.load().gpmdm_pf_observation(self._h, _lib.dptr(mean), _lib.dptr(var), self._stream()),
+                   "current_observation")
+        if spread:
+            return torch.from_numpy(mean), torch.from_numpy(var)
+        return torch.from_numpy(mean)
+
+    def current_observation_mean(self) -> torch.Tensor:
+        """``current_observation``'s mean alone: the observation-space counterpart of
+        ``current_state_mean``."""
+        return self.current_observation(spread=False)
 
     @property
     def frame(self) -> int:

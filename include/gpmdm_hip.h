@@ -442,6 +442,33 @@ int gpmdm_pf_health(gpmdm_pf_t pf, int64_t* counts, int reset, void* stream);
  * mean: F x d host (F = 1 for a single filter).  Synchronises `stream`. */
 int gpmdm_pf_predict(gpmdm_pf_t pf, double* mean, void* stream);
 
+/* Masked observations: missing joints.  observed: D bytes (non-zero = this dimension of z is
+ * observed) or NULL (all observed, the default).  Holds until changed.  Between frames only
+ * (GPMDM_E_STATE inside a step); a pending pre-switch stays pending.  A masked frame computes
+ * the reference's likelihood (gpmdm_pf.py:170-192) on the model restricted to the observed
+ * dimensions -- the same kernels, with lambda^2 = 0 at the unobserved ones and D, sum log
+ * il2 and the float32 constant taken over the observed ones.  z at the unobserved positions
+ * is replaced by 0 in the library's staging copy (the caller's array is not written), so a
+ * NaN there reaches no kernel.  With no dimension observed the frame is a pure prediction
+ * step: no observation kernel runs, ll is exactly 0 and w exactly 1/P.  gpmdm_pf_step,
+ * gpmdm_pf_propagate and gpmdm_pf_weigh honour it; every rank of a sharded filter must hold
+ * the same mask (gpmdm_pf_propagate_multi: GPMDM_E_INVALID otherwise).  Filter banks:
+ * GPMDM_E_INVALID (their filters share one lambda^2 per tile). */
+int gpmdm_pf_set_obs_mask(gpmdm_pf_t pf, const uint8_t* observed);
+
+/* The filtered pose: the observation-space read-out of the particles the filter holds now
+ * (post-resample, equal weights):
+ *   mean[j]   = (1/P) sum_p mu_j(x_p),  mu = the observation GP's mean (gpmdm.py:955-957)
+ *   spread[j] = (1/P) sum_p (mu_j(x_p) - mean[j])^2   (may be NULL)
+ * Host outputs, D doubles each.  Reads the particle states only: no draw, no state change, a
+ * pending pre-switch stays pending; a mask or the cutoff do not enter (every dimension is
+ * read out: the unobserved ones are the filter's imputation).  Valid any time after init /
+ * import.  A mean-only GP tile of its own (csrc/obs_readout.h); fixed-order reductions, so
+ * the same cloud gives bitwise the same values on every call.  A sharded filter evaluates
+ * its replicated cloud on the handle it is called on.  Synchronises `stream`; with mean and
+ * spread both NULL the kernels are launched only (timing).  Banks: GPMDM_E_INVALID. */
+int gpmdm_pf_observation(gpmdm_pf_t pf, double* mean, double* spread, void* stream);
+
 /* Device-side GP factor: the recipe of _precompute_kernel_inverses
  * (gpmdm.py:1284-1305) for one GP block -- the observation GP, or one class block of the
  * dynamics GP (the reference's full masked matrix has exact zeros off the class blocks):
