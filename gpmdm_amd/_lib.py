@@ -43,6 +43,17 @@ class ModelDesc(ctypes.Structure):
     ]
 
 
+GPMDM_FORECAST_SAMPLE, GPMDM_FORECAST_MEAN = 0, 1
+GPMDM_FORECAST_MAX_HORIZON = 4096
+FORECAST_MODES = {"sample": GPMDM_FORECAST_SAMPLE, "mean": GPMDM_FORECAST_MEAN}
+
+
+class ForecastOut(ctypes.Structure):
+    """gpmdm_forecast_out: host arrays, any may be NULL."""
+    _fields_ = [("class_prob", _dp), ("state_mean", _dp), ("obs_mean", _dp), ("obs_spread", _dp),
+                ("states", _dp), ("classes", _i64p)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "gpmdm_model_create": (c_int, [POINTER(ModelDesc), c_int, POINTER(c_void_p)]),
@@ -93,6 +104,7 @@ _SIGS = {
     "gpmdm_pf_predict": (c_int, [c_void_p, _dp, c_void_p]),
     "gpmdm_pf_set_obs_mask": (c_int, [c_void_p, c_void_p]),
     "gpmdm_pf_observation": (c_int, [c_void_p, _dp, _dp, c_void_p]),
+    "gpmdm_pf_forecast": (c_int, [c_void_p, c_int, c_int, POINTER(c_uint64), POINTER(ForecastOut), c_void_p]),
     "gpmdm_pf_set_comm": (c_int, [c_void_p, c_void_p, c_int]),
     "gpmdm_comm_unique_id": (c_int, [c_void_p]),
     "gpmdm_comm_init": (c_int, [c_int, c_int, c_void_p, c_int, POINTER(c_void_p)]),

@@ -1,0 +1,273 @@
+// C ABI, the forecast roll-out (gpmdm_pf_forecast): H steps of the filter's proposal on a
+// scratch copy of the cloud, all queued on the caller's stream -- per step the roll-out switch,
+// the filter's grouping passes on the forecast's own tables, the dynamics-GP tiles as predict()
+// launches them, the roll-out finish and reduce, and the pose read-out pointed at the scratch
+// cloud -- then one copy-back and one wait.  Kernels: forecast.h.
+#include "capi_internal.h"
+#include "forecast.h"
+
+namespace gpmdm::capi {
+
+// staging of the per-step clouds may take this much device memory (H x P x (d + 1) doubles)
+constexpr size_t kForecastStageBytes = (size_t)1 << 30;
+
+// the forecast's class tables: the layout of gpmdm_pf::small's (class_start, counts, segments)
+struct FcTables {
+  int* t;
+  int* class_start() const { return t; }
+  int* counts() const { return t + 40; }
+  int* seg_begin() const { return t + 80; }
+  int* seg_end() const { return t + 120; }
+  int* seg_out() const { return t + 160; }
+  int* seg_tiles() const { return t + 200; }
+};
+
+static int ensure_scratch(gpmdm_pf* pf, int H, bool obs) {
+  const gpmdm_model* m = pf->m;
+  const int C = m->C, d = m->d, D = m->D;
+  const long long P = pf->P;
+  const long long nb = cdiv(P, 256);
+#define NEED(ptr, n) do { if (!(ptr)) TRY(dalloc(&(ptr), (size_t)(n))); } while (0)
+  for (int k = 0; k < 2; ++k) {
+    NEED(pf->fc_X[k], P * d);
+    NEED(pf->fc_cls[k], P);
+  }
+  NEED(pf->fc_perm, P);
+  NEED(pf->fc_blockcounts, nb * C);
+  NEED(pf->fc_blockoff, nb * C);
+  NEED(pf->fc_mu, P * d);
+  NEED(pf->fc_part, nb * d);
+  NEED(pf->fc_tab, 256);
+#undef NEED
+  const size_t qn = (size_t)pf->nparts_dyn_max * P;
+  if (pf->fc_q_cap < qn) {
+    dfree(pf->fc_q);
+    pf->fc_q_cap = 0;
+    TRY(dalloc(&pf->fc_q, qn));
+    pf->fc_q_cap = qn;
+  }
+  if (obs && !pf->fc_ro_part) TRY(dalloc(&pf->fc_ro_part, readout_part_doubles(P, D)));
+  const size_t on = (size_t)H * (C + d + 2 * D);
+  if (pf->fc_out_cap < on) {
+    dfree(pf->fc_out);
+    hfree(pf->fc_pin);
+    pf->fc_out_cap = 0;
+    TRY(dalloc(&pf->fc_out, on));
+    TRY(halloc(&pf->fc_pin, on, 0));
+    pf->fc_out_cap = on;
+  }
+  if (!pf->fc_ev) HIPCHK(hipEventCreateWithFlags(&pf->fc_ev, hipEventDisableTiming));
+  return GPMDM_OK;
+}
+
+// Every launch of the roll-out.  stage_X / stage_cls (or nullptr): H x P x d / H x P device
+// rows that take each step's cloud instead of the ping-pong halves (the next step reads its
+// input there: no copy).
+static int launch_rollout(gpmdm_pf* pf, int H, bool mean_only, bool obs, unsigned seed_lo, unsigned seed_hi,
+                          double* stage_X, int* stage_cls, hipStream_t s) {
+  gpmdm_model* m = pf->m;
+  const int C = m->C, d = m->d, D = m->D;
+  const long long P = pf->P;
+  const int nb = (int)cdiv(P, 256);
+  const int W = C + d + 2 * D;
+  const std::vector<GpImage>& dset = m->dyn_set(true);   // every particle is evaluated: predict()'s images
+  const FcTables tb{pf->fc_tab};
+  const double* Xcur = pf->X;
+  const int* ccur = pf->cls;
+  for (int h = 0; h < H; ++h) {
+    double* Xnext = stage_X ? stage_X + (size_t)h * P * d : pf->fc_X[h & 1];
+    if (!mean_only || h == 0) {         // (mean mode: classes frozen, one grouping serves every step)
+      const int* cgrp = ccur;
+      if (mean_only) {
+        launch_class_hist(ccur, P, C, pf->fc_blockcounts, s);
+      } else {
+        int* cnext = stage_cls ? stage_cls + (size_t)h * P : pf->fc_cls[h & 1];
+        FcSwitchArgs sa{};
+        sa.P = P;
+        sa.C = C;
+        sa.h = (unsigned)(h + 1);
+        sa.frame = pf->frame;
+        sa.seed_lo = seed_lo;
+        sa.seed_hi = seed_hi;
+        sa.cls = ccur;
+        sa.cls_new = cnext;
+        sa.T = pf->T;
+        sa.blockcounts = pf->fc_blockcounts;
+        launch_fc_switch(sa, s);
+        cgrp = ccur = cnext;
+      }
+      ScanArgs sc{};
+      sc.nb = nb;
+      sc.C = C;
+      sc.pt = dset[0].geo.pt();
+      sc.lo = 0;
+      sc.hi = P;
+      sc.blockcounts = pf->fc_blockcounts;
+      sc.cls_new = cgrp;
+      sc.blockoff = pf->fc_blockoff;
+      sc.class_start = tb.class_start();
+      sc.counts = tb.counts();
+      sc.seg_pos_begin = tb.seg_begin();
+      sc.seg_pos_end = tb.seg_end();
+      sc.seg_out_base = tb.seg_out();
+      sc.seg_tile_start = tb.seg_tiles();
+      launch_scan_counts(sc, s);
+      GroupArgs ga{};
+      ga.P = P;
+      ga.n = P;
+      ga.C = C;
+      ga.cls_new = cgrp;
+      ga.class_start = tb.class_start();
+      ga.blockoff = pf->fc_blockoff;
+      ga.perm = pf->fc_perm;
+      launch_group(ga, s);
+    }
+    // each class's dynamics GP on the scratch cloud, rows in grouped order (gpmdm_pf_predict)
+    for (int c0 = 0; c0 < C; c0 += kMaxSeg) {
+      const int ns = std::min(kMaxSeg, C - c0);
+      TileParams tp{};
+      int njm = 0;
+      for (int k = 0; k < ns; ++k) {
+        tp.seg[k] = dset[c0 + k].seg();
+        njm = std::max(njm, dset[c0 + k].n_j);
+      }
+      tp.n_seg = ns;
+      tp.geo = dset[c0].geo;
+      tp.tiles_ub = (int)(cdiv(P, tp.geo.pt()) + ns);
+      tp.n_j_max = njm;
+      tp.seg_pos_begin = tb.seg_begin() + c0;
+      tp.seg_pos_end = tb.seg_end() + c0;
+      tp.seg_out_base = tb.seg_out() + c0;
+      tp.seg_tile_start = tb.seg_tiles() + c0;
+      tp.perm = pf->fc_perm;
+      tp.X = Xcur;
+      fill_tile_common(tp, m, true);
+      tp.qpart = pf->fc_q;
+      tp.ld_q = P;
+      tp.mu = pf->fc_mu;
+      tp.ld_mu = d;
+      launch_gp_tile(tp, d, true, s);
+    }
+    FcFinishArgs fa{};
+    fa.P = P;
+    fa.C = C;
+    fa.d = d;
+    fa.mean_only = mean_only ? 1 : 0;
+    fa.h = (unsigned)(h + 1);
+    fa.frame = pf->frame;
+    fa.seed_lo = seed_lo;
+    fa.seed_hi = seed_hi;
+    fa.seg_out_base = tb.seg_out();
+    fa.seg_pos_begin = tb.seg_begin();
+    fa.perm = pf->fc_perm;
+    for (int c = 0; c < C; ++c) fa.n_parts[c] = dset[c].n_parts();
+    fa.qpart = pf->fc_q;
+    fa.ld_q = P;
+    fa.mu = pf->fc_mu;
+    fa.X = Xcur;
+    for (int j = 0; j <= d; ++j) fa.lin_c2[j] = m->x_lin_c2[j];
+    for (int j = 0; j < d; ++j) fa.il2[j] = m->x_il2[j];
+    fa.X_out = Xnext;
+    fa.partials = pf->fc_part;
+    launch_fc_finish(fa, s);
+    FcReduceArgs ra{};
+    ra.P = P;
+    ra.C = C;
+    ra.d = d;
+    ra.nb = nb;
+    ra.counts = tb.counts();
+    ra.partials = pf->fc_part;
+    ra.out = pf->fc_out + (size_t)h * W;
+    launch_fc_reduce(ra, s);
+    if (obs) {
+      ReadoutParams rp{};
+      rp.X = Xnext;
+      rp.P = P;
+      rp.d = d;
+      rp.D = D;
+      rp.ls = m->y_ls_dev;
+      rp.Xrec = m->obs.Xrec;
+      rp.nks = ksteps((int)m->N);
+      rp.Bro = m->ro_beta;
+      rp.n_groups = readout_groups(D);
+      rp.part = pf->fc_ro_part;
+      rp.out = pf->fc_out + (size_t)h * W + C + d;   // {mean[D], spread[D]} of row h
+      launch_obs_readout(rp, s);
+    }
+    Xcur = Xnext;
+    HIPCHK(hipGetLastError());
+  }
+  return GPMDM_OK;
+}
+
+}  // namespace gpmdm::capi
+
+extern "C" {
+
+int gpmdm_pf_forecast(gpmdm_pf_t pf, int horizon, int mode, const uint64_t* seed, const gpmdm_forecast_out* out,
+                      void* stream) {
+  CHECK(pf, "null handle");
+  CHECK(pf->F == 1, "the forecast serves single filters, not banks");
+  CHECK(horizon >= 1 && horizon <= GPMDM_FORECAST_MAX_HORIZON, "horizon must be in [1, GPMDM_FORECAST_MAX_HORIZON]");
+  CHECK(mode == GPMDM_FORECAST_SAMPLE || mode == GPMDM_FORECAST_MEAN, "mode: GPMDM_FORECAST_SAMPLE or GPMDM_FORECAST_MEAN");
+  if (!pf->initialised) return fail(GPMDM_E_STATE, "particle filter not initialised");
+  // (a pending pre-switch reads the cloud and writes the step's tables: neither is the forecast's)
+  if ((pf->switched && !pf->preswitched) || pf->dyn_done || pf->propagated)
+    return fail(GPMDM_E_STATE, "forecast between switch and resample");
+  gpmdm_model* m = pf->m;
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int C = m->C, d = m->d, D = m->D, H = horizon;
+  const long long P = pf->P;
+  const int W = C + d + 2 * D;
+  const bool mean_only = mode == GPMDM_FORECAST_MEAN;
+  static const gpmdm_forecast_out none{};
+  const gpmdm_forecast_out& o = out ? *out : none;
+  const bool obs = o.obs_mean || o.obs_spread;
+  if (o.states || o.classes)
+    CHECK((size_t)H * (size_t)P * (size_t)(d + 1) <= kForecastStageBytes / sizeof(double),
+          "states / classes of this forecast need more than 1 GiB of device staging (H x P x (d + 1) doubles)");
+  const unsigned long long sd = seed ? *seed : (((unsigned long long)pf->seed_hi << 32) | pf->seed_lo);
+  TRY(ensure_scratch(pf, H, obs));
+  // per-call staging of the clouds, released in the stream's order on every exit
+  double* stage_X = nullptr;
+  int* stage_cls = nullptr;
+  if (o.states) TRY(dalloc(&stage_X, (size_t)H * P * d));
+  if (o.classes && !mean_only && dalloc(&stage_cls, (size_t)H * P) != GPMDM_OK) {
+    dfree(stage_X);
+    return GPMDM_E_NOMEM;
+  }
+  int rc = launch_rollout(pf, H, mean_only, obs, (unsigned)(sd & 0xffffffffu), (unsigned)(sd >> 32), stage_X,
+                          stage_cls, s);
+  std::vector<int> c32;
+  auto copies = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(pf->fc_pin, pf->fc_out, sizeof(double) * H * W, hipMemcpyDeviceToHost, s));
+    if (o.states) HIPCHK(hipMemcpyAsync(o.states, stage_X, sizeof(double) * H * P * d, hipMemcpyDeviceToHost, s));
+    if (o.classes) {
+      c32.resize((size_t)(mean_only ? 1 : H) * P);   // (mean mode: the filter's classes, every step)
+      HIPCHK(hipMemcpyAsync(c32.data(), mean_only ? pf->cls : stage_cls, sizeof(int) * c32.size(),
+                            hipMemcpyDeviceToHost, s));
+    }
+    return GPMDM_OK;
+  };
+  if (rc == GPMDM_OK) rc = copies();
+  const bool marked = hipEventRecord(pf->fc_ev, s) == hipSuccess;
+  pf->fc_pending = marked;               // (quiesce waits for the launches if the wait below fails)
+  if (stage_X) dfree_after(stage_X, s);
+  if (stage_cls) dfree_after(stage_cls, s);
+  if (rc != GPMDM_OK) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  pf->fc_pending = false;
+  for (int h = 0; h < H; ++h) {
+    const double* row = pf->fc_pin + (size_t)h * W;
+    if (o.class_prob) std::memcpy(o.class_prob + (size_t)h * C, row, sizeof(double) * C);
+    if (o.state_mean) std::memcpy(o.state_mean + (size_t)h * d, row + C, sizeof(double) * d);
+    if (o.obs_mean) std::memcpy(o.obs_mean + (size_t)h * D, row + C + d, sizeof(double) * D);
+    if (o.obs_spread) std::memcpy(o.obs_spread + (size_t)h * D, row + C + d + D, sizeof(double) * D);
+  }
+  if (o.classes)
+    for (size_t i = 0; i < (size_t)H * P; ++i) o.classes[i] = c32[mean_only ? i % (size_t)P : i];
+  return GPMDM_OK;
+}
+
+}  // extern "C"

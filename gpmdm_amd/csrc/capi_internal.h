@@ -6,6 +6,7 @@
 //   capi_frame.hip     the per-frame launch sequence: switch, propagate, weigh, resample, read
 //   capi_exchange.hip  the multi-rank exchange (pack / unpack, RCCL communicator, gathers)
 //   capi_replay.hip    replay-draw staging (pinned buffers, staged normals, pre-switch)
+//   capi_forecast.hip  the multi-step forecast roll-out (gpmdm_pf_forecast)
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -323,6 +324,23 @@ struct gpmdm_pf {
   double *ro_part = nullptr, *ro_obs = nullptr, *ro_obs_pin = nullptr;
   hipEvent_t ro_obs_ev = nullptr;
   bool ro_obs_pending = false;
+  // The forecast roll-out (gpmdm_pf_forecast, forecast.h; capi_forecast.hip): scratch of its
+  // own, allocated on first use -- the two halves of the ping-pong cloud, the grouping's
+  // tables (the layout of `small`'s, base 0), block counts / offsets and permutation, the
+  // dynamics tiles' outputs, the finish's block sums, the pose read-out's partials, and the
+  // H x (C + d + 2 D) result rows with their pinned landing buffer (grown on demand).  None
+  // of it is shared with the step, the pre-switch, predict() or the read-out, so a forecast
+  // leaves a pending pre-switch pending.  fc_ev follows a forecast's launches (quiesce waits
+  // for it while fc_pending: the call itself synchronises, so only after a failed one).
+  double* fc_X[2] = {nullptr, nullptr};
+  int* fc_cls[2] = {nullptr, nullptr};
+  int *fc_perm = nullptr, *fc_blockcounts = nullptr, *fc_blockoff = nullptr, *fc_tab = nullptr;
+  double *fc_q = nullptr, *fc_mu = nullptr, *fc_part = nullptr, *fc_ro_part = nullptr;
+  size_t fc_q_cap = 0;
+  double *fc_out = nullptr, *fc_pin = nullptr;
+  size_t fc_out_cap = 0;
+  hipEvent_t fc_ev = nullptr;
+  bool fc_pending = false;
   // likelihood finish deferred into the resampling launch (single-shard small filters:
   // k_small_resample computes ll first, one launch less per frame); flush_ll runs it for
   // any reader of ll that comes first
@@ -643,6 +661,12 @@ struct gpmdm_pf {
     dfree(ro_obs);
     hfree(ro_obs_pin);
     if (ro_obs_ev) (void)hipEventDestroy(ro_obs_ev);
+    double* fd[] = {fc_X[0], fc_X[1], fc_q, fc_mu, fc_part, fc_ro_part, fc_out};
+    for (double* p : fd) dfree(p);
+    int* fi[] = {fc_cls[0], fc_cls[1], fc_perm, fc_blockcounts, fc_blockoff, fc_tab};
+    for (int* p : fi) dfree(p);
+    hfree(fc_pin);
+    if (fc_ev) (void)hipEventDestroy(fc_ev);
     dfree(bmax);
     dfree(bmax_rows);
     dfree(owner);

@@ -304,6 +304,10 @@ int quiesce(gpmdm_pf* pf) {
     HIPCHK(hipEventSynchronize(pf->ro_obs_ev));
     pf->ro_obs_pending = false;
   }
+  if (pf->fc_pending) {                // a forecast that failed before its own wait
+    HIPCHK(hipEventSynchronize(pf->fc_ev));
+    pf->fc_pending = false;
+  }
   return GPMDM_OK;
 }
 
@@ -638,6 +642,8 @@ int gpmdm_pf_set_model(gpmdm_pf_t pf, gpmdm_model_t m) {
   dfree(pf->sobs);
   dfree(pf->pred_q);
   pf->pred_q_cap = 0;
+  dfree(pf->fc_q);                     // (the forecast's tile partials: as predict's)
+  pf->fc_q_cap = 0;
   pf->qdyn = qdyn;
   pf->qobs = qobs;
   pf->sobs = sobs;

@@ -143,7 +143,15 @@ __device__ __forceinline__ double u01_oo(unsigned hi, unsigned lo) {   // (0, 1)
   return ((double)x + 0.5) * 0x1.0p-53;
 }
 
-enum RngStream : unsigned { kStreamSwitch = 0, kStreamDyn = 1, kStreamResample = 2, kStreamSystematic = 3 };
+enum RngStream : unsigned {
+  kStreamSwitch = 0,
+  kStreamDyn = 1,
+  kStreamResample = 2,
+  kStreamSystematic = 3,
+  // the forecast roll-out's draws (forecast.h): sub = (horizon step << 8) | pair
+  kStreamForecastSwitch = 4,
+  kStreamForecastDyn = 5
+};
 
 // Order-preserving uint64 image of a double (atomicMax on doubles).
 __device__ __forceinline__ unsigned long long ord_enc(double x) {

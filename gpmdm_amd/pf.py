@@ -54,6 +54,8 @@ from __future__ import annotations
 
 import ctypes
 import os
+from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -81,6 +83,17 @@ def device_shard_plan(P: int, devices, repeat: bool = False) -> list:
         raise ValueError(f"bad device index in {devs}")
     R = len(devs)
     return [(dev, r, P * r // R, P * (r + 1) // R) for r, dev in enumerate(devs)]
+
+
+@dataclass
+class Forecast:
+    """``GPMDM_PF.forecast``'s result; row h - 1 is h frames ahead."""
+    class_probabilities: torch.Tensor                   # (H, C)
+    state_mean: torch.Tensor                            # (H, d)
+    observation_mean: Optional[torch.Tensor] = None     # (H, D)
+    observation_spread: Optional[torch.Tensor] = None   # (H, D)
+    states: Optional[torch.Tensor] = None               # (H, P, d)
+    classes: Optional[torch.Tensor] = None              # (H, P) int64
 
 
 def _as_f64_vector(z) -> np.ndarray:
@@ -533,6 +546,46 @@ class GPMDM_PF:
         """``current_observation``'s mean alone: the observation-space counterpart of
         ``current_state_mean``."""
         return self.current_observation(spread=False)
+
+    def forecast(self, horizon: int, *, mode: str = "sample", observation: bool = True,
+                 particles: bool = False, seed=None) -> Forecast:
+        """Where the pose, the latent state and the activity will be 1..``horizon`` frames from
+        now: the filter's own proposal (Markov switch, then the new class's dynamics GP with its
+        noise; gpmdm_pf.py:137-168) rolled out ``horizon`` times on a scratch copy of the
+        particles it holds now, without weighting or resampling, all on the device
+        (gpmdm_pf_forecast).  Row h - 1 of each result is h frames ahead: the class fractions
+        and mean state of the roll-out cloud, with ``observation`` the pose read-out of
+        ``current_observation`` on it (mean and cloud spread), with ``particles`` the cloud
+        itself.  ``mode="mean"`` is the deterministic variant (classes frozen, no noise; its
+        first ``state_mean`` is ``predict()``'s).
+
+        The draws are the device's Philox streams whatever the filter's ``rng``, keyed by
+        ``seed`` (default: the filter's) and the current ``frame``: the same cloud, frame and
+        seed give bitwise the same forecast, and a shorter horizon gives the first rows of a
+        longer one.  The filter is not changed: no state change, no draw from torch's
+        generator, and later updates are bitwise those without the call.  A sharded filter
+        forecasts its replicated cloud on rank 0."""
+        if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)):
+            raise ValueError(f"horizon must be an integer, got {horizon!r}")
+        H = int(horizon)
+        if not 1 <= H <= _lib.GPMDM_FORECAST_MAX_HORIZON:
+            raise ValueError(f"horizon must be in [1, {_lib.GPMDM_FORECAST_MAX_HORIZON}], got {H}")
+        if mode not in _lib.FORECAST_MODES:
+            raise ValueError(f"mode must be one of {sorted(_lib.FORECAST_MODES)}, got {mode!r}")
+        self._sync_model()
+        P, C, d, D = self._num_particles, self.num_classes, self.latent_dim, self.observation_dim
+        cp, sm = np.zeros((H, C)), np.zeros((H, d))
+        om = np.zeros((H, D)) if observation else None
+        osp = np.zeros((H, D)) if observation else None
+        st = np.zeros((H, P, d)) if particles else None
+        cl = np.zeros((H, P), dtype=np.int64) if particles else None
+        out = _lib.ForecastOut(_lib.dptr(cp), _lib.dptr(sm), _lib.dptr(om), _lib.dptr(osp), _lib.dptr(st),
+                               _lib.i64ptr(cl))
+        sd = None if seed is None else ctypes.byref(ctypes.c_uint64(int(seed) & (2 ** 64 - 1)))
+        _lib.check(_lib.load().gpmdm_pf_forecast(self._h, H, _lib.FORECAST_MODES[mode], sd, ctypes.byref(out),
+                                                 self._stream()), "forecast")
+        t = lambda a: None if a is None else torch.from_numpy(a)   # noqa: E731
+        return Forecast(t(cp), t(sm), t(om), t(osp), t(st), t(cl))
 
     @property
     def frame(self) -> int:

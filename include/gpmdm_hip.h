@@ -469,6 +469,50 @@ int gpmdm_pf_set_obs_mask(gpmdm_pf_t pf, const uint8_t* observed);
  * spread both NULL the kernels are launched only (timing).  Banks: GPMDM_E_INVALID. */
 int gpmdm_pf_observation(gpmdm_pf_t pf, double* mean, double* spread, void* stream);
 
+/* Multi-step forecast: class, latent state and pose h = 1..horizon frames ahead.  Starting from
+ * the particles the filter holds now (post-resample, equal weights), a scratch copy of the
+ * cloud runs the filter's own proposal `horizon` times, with no weighting and no resampling:
+ *   1. switch    c <- argmax_j T[c, j] / E_j, first maximum (gpmdm_pf.py:137-151)
+ *   2. propagate x <- mu_c(x) + sqrt(var_c(x)) eps with the new class's dynamics GP
+ *                (gpmdm.py:1032-1068, gpmdm_pf.py:153-168)
+ *   3. read out, into row h - 1 of each output that is not NULL:
+ *        class_prob[c] = (particles in class c) / P,  state_mean = (1/P) sum_p x_p,
+ *        obs_mean / obs_spread = gpmdm_pf_observation's mean and cloud variance of that cloud
+ *        (the observation GP's own predictive variance does not enter),
+ *        states / classes = the roll-out cloud after the step.
+ * GPMDM_FORECAST_MEAN is the deterministic variant: no switch and no noise (classes frozen,
+ * x <- mu_c(x)); its first state_mean is gpmdm_pf_predict's mean up to summation order.
+ * Draws: always the device's Philox4x32-10, whatever the filter's rng mode, with the key of
+ * *seed (NULL: the handle's seed) and the counter
+ *   (particle index, the handle's frame, stream, (h << 8) | pair),  stream 4 = the switch's
+ *   Exp(1) draws, 5 = the dynamics normals, pair = j >> 1 of class / dimension j,
+ * through the transforms of the filter's own draws (E = -log u, u in (0, 1); Box-Muller from a
+ * (0, 1) and a [0, 1) uniform).  So a forecast is a function of (cloud, frame, seed) alone, and
+ * rows [0, k) of a longer forecast equal the forecast of horizon k bitwise; every reduction has
+ * a fixed order.
+ * The live filter is untouched: no state change, no draw from the host generator, no frame
+ * added to the Philox counter, no health counter; a pending pre-switch stays pending (the
+ * roll-out has scratch and class tables of its own, allocated on first use and kept on the
+ * handle).  All steps are queued on `stream` without a host wait in between; the call copies the
+ * results back and synchronises `stream` once.  With obs_mean and obs_spread both NULL no
+ * observation kernel is launched.  states / classes are staged on the device in H x P x (d + 1)
+ * doubles for the call's duration: GPMDM_E_INVALID above 1 GiB.  horizon in
+ * [1, GPMDM_FORECAST_MAX_HORIZON].  Between a switch and its resample: GPMDM_E_STATE.  A
+ * sharded filter forecasts its replicated cloud on the handle it is called on.  Banks:
+ * GPMDM_E_INVALID. */
+enum { GPMDM_FORECAST_SAMPLE = 0, GPMDM_FORECAST_MEAN = 1 };
+#define GPMDM_FORECAST_MAX_HORIZON 4096
+typedef struct gpmdm_forecast_out {   /* host arrays; any may be NULL */
+  double*  class_prob;   /* H x C */
+  double*  state_mean;   /* H x d */
+  double*  obs_mean;     /* H x D */
+  double*  obs_spread;   /* H x D */
+  double*  states;       /* H x P x d : the roll-out cloud after each step */
+  int64_t* classes;      /* H x P */
+} gpmdm_forecast_out;
+int gpmdm_pf_forecast(gpmdm_pf_t pf, int horizon, int mode, const uint64_t* seed,
+                      const gpmdm_forecast_out* out, void* stream);
+
 /* Device-side GP factor: the recipe of _precompute_kernel_inverses
  * (gpmdm.py:1284-1305) for one GP block -- the observation GP, or one class block of the
  * dynamics GP (the reference's full masked matrix has exact zeros off the class blocks):
