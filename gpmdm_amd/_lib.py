@@ -54,6 +54,15 @@ class ForecastOut(ctypes.Structure):
                 ("states", _dp), ("classes", _i64p)]
 
 
+GPMDM_SMOOTH_MAX_LAG = 4096
+
+
+class SmoothedOut(ctypes.Structure):
+    """gpmdm_smoothed_out: host arrays, any may be NULL."""
+    _fields_ = [("class_prob", _dp), ("state_mean", _dp), ("distinct", _i64p), ("obs_mean", _dp),
+                ("obs_spread", _dp), ("ancestors", _i64p), ("states", _dp), ("classes", _i64p)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "gpmdm_model_create": (c_int, [POINTER(ModelDesc), c_int, POINTER(c_void_p)]),
@@ -105,6 +114,9 @@ _SIGS = {
     "gpmdm_pf_set_obs_mask": (c_int, [c_void_p, c_void_p]),
     "gpmdm_pf_observation": (c_int, [c_void_p, _dp, _dp, c_void_p]),
     "gpmdm_pf_forecast": (c_int, [c_void_p, c_int, c_int, POINTER(c_uint64), POINTER(ForecastOut), c_void_p]),
+    "gpmdm_pf_set_smoothing": (c_int, [c_void_p, c_int]),
+    "gpmdm_pf_smoothing_depth": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "gpmdm_pf_smoothed": (c_int, [c_void_p, c_int, c_int, POINTER(SmoothedOut), c_void_p]),
     "gpmdm_pf_set_comm": (c_int, [c_void_p, c_void_p, c_int]),
     "gpmdm_comm_unique_id": (c_int, [c_void_p]),
     "gpmdm_comm_init": (c_int, [c_int, c_int, c_void_p, c_int, POINTER(c_void_p)]),

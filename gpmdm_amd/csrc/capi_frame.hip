@@ -740,6 +740,7 @@ int gpmdm_pf_resample(gpmdm_pf_t pf, const double* uniforms, void* stream) {
   }
   pf->frame += 1;
   pf->propagated = false;
+  if (pf->sm_L > 0) TRY(sm_record(pf, s));   // smoothing: this frame into the ancestry ring
   if (pf->preswitch) {                 // the next frame's switch, behind the read-out
     TRY(do_switch(pf, nullptr, nullptr, s, pf->order_wanted()));
     pf->sw_stream = s;

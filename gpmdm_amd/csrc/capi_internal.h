@@ -7,6 +7,7 @@
 //   capi_exchange.hip  the multi-rank exchange (pack / unpack, RCCL communicator, gathers)
 //   capi_replay.hip    replay-draw staging (pinned buffers, staged normals, pre-switch)
 //   capi_forecast.hip  the multi-step forecast roll-out (gpmdm_pf_forecast)
+//   capi_smooth.hip    fixed-lag smoothing: the ancestry ring and its read-out (gpmdm_pf_smoothed)
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -341,6 +342,29 @@ struct gpmdm_pf {
   size_t fc_out_cap = 0;
   hipEvent_t fc_ev = nullptr;
   bool fc_pending = false;
+  // Fixed-lag smoothing (gpmdm_pf_set_smoothing / gpmdm_pf_smoothed, smooth.h;
+  // capi_smooth.hip).  sm_L > 0: every resample records {ridx, cls, X} into slot
+  // frame mod (sm_L + 1) of the ring (sm_anc / sm_cls / sm_X, sm_L + 1 frames each); sm_depth =
+  // min(sm_L, frames recorded since the ring was last cleared), the root of a cleared ring
+  // being the cloud the filter held then (sm_clear records it).  The record launch follows the
+  // frame's read-out number, which quiesce takes for the frame's last work: sm_ev is recorded
+  // behind every record launch (smoothing on only) and quiesce waits for it while sm_pending.
+  // The read-out's scratch -- class counts, block sums, marks, result rows with their pinned
+  // landing buffer, the pose read-out's partials -- is its own, allocated on first use and grown
+  // on demand; sm_tr_ev follows a read-out's launches (waited for while sm_tr_pending: the call
+  // itself synchronises, so only after a failed one).
+  int sm_L = 0, sm_depth = 0;
+  int* sm_anc = nullptr;
+  int* sm_cls = nullptr;
+  double* sm_X = nullptr;
+  hipEvent_t sm_ev = nullptr, sm_tr_ev = nullptr;
+  hipStream_t sm_stream = nullptr;    // the stream of the last record launch
+  bool sm_pending = false, sm_tr_pending = false;
+  int* sm_counts = nullptr;
+  double *sm_part = nullptr, *sm_out = nullptr, *sm_pin = nullptr, *sm_ro_part = nullptr;
+  unsigned char* sm_marks = nullptr;
+  size_t sm_counts_cap = 0, sm_part_cap = 0, sm_out_cap = 0, sm_marks_cap = 0;
+  int sm_slot() const { return (int)(frame % (unsigned)(sm_L + 1)); }   // the latest frame's
   // likelihood finish deferred into the resampling launch (single-shard small filters:
   // k_small_resample computes ll first, one launch less per frame); flush_ll runs it for
   // any reader of ll that comes first
@@ -667,6 +691,17 @@ struct gpmdm_pf {
     for (int* p : fi) dfree(p);
     hfree(fc_pin);
     if (fc_ev) (void)hipEventDestroy(fc_ev);
+    dfree(sm_anc);
+    dfree(sm_cls);
+    dfree(sm_X);
+    dfree(sm_counts);
+    dfree(sm_part);
+    dfree(sm_out);
+    dfree(sm_ro_part);
+    dfree(sm_marks);
+    hfree(sm_pin);
+    if (sm_ev) (void)hipEventDestroy(sm_ev);
+    if (sm_tr_ev) (void)hipEventDestroy(sm_tr_ev);
     dfree(bmax);
     dfree(bmax_rows);
     dfree(owner);
@@ -730,6 +765,11 @@ int flush_ll(gpmdm_pf* pf, hipStream_t s);
 int drop_preswitch(gpmdm_pf* pf, hipStream_t s, bool host_wait);
 int quiesce(gpmdm_pf* pf);
 int quiesce_users(gpmdm_model* m);
+// smoothing (capi_smooth.hip): wait for the record / read-out launches in flight; record the
+// frame just resampled on s; forget the history and record the current cloud as its root on s
+int sm_wait(gpmdm_pf* pf);
+int sm_record(gpmdm_pf* pf, hipStream_t s);
+int sm_clear(gpmdm_pf* pf, hipStream_t s);
 int h2d(void* dst, const void* src, size_t bytes);
 // the observation-GP cutoff image (capi_model.hip; packed on the host or the device)
 struct CutoffPlan {

@@ -308,6 +308,9 @@ int quiesce(gpmdm_pf* pf) {
     HIPCHK(hipEventSynchronize(pf->fc_ev));
     pf->fc_pending = false;
   }
+  // a smoothing record follows the frame's read-out number on the frame's stream; a smoothed
+  // read-out that failed before its own wait
+  TRY(sm_wait(pf));
   return GPMDM_OK;
 }
 
@@ -408,7 +411,7 @@ int gpmdm_pf_init(gpmdm_pf_t pf, const double* states, const int64_t* classes) {
   pf->own_valid = false;               // no ancestors yet: identity ownership
   pf->rows_st = pf->rows_ll = nullptr;
   pf->switched = pf->propagated = pf->dyn_done = pf->ll_pending = pf->gemm_ahead = false;
-  return GPMDM_OK;
+  return sm_clear(pf, ls);             // smoothing: this cloud is the history's root
 }
 
 // Restore an exported state (gpmdm_pf.py:78-82, 100-104): particles, ancestors, ll and the
@@ -484,7 +487,7 @@ int gpmdm_pf_import(gpmdm_pf_t pf, const double* states, const int64_t* classes,
   if (pf->seq_pin) pf->ro_seq = pf->seq_min();   // (synchronised: nothing to wait for)
   pf->initialised = true;
   pf->switched = pf->propagated = pf->dyn_done = pf->gemm_ahead = false;
-  return GPMDM_OK;
+  return sm_clear(pf, ls);             // smoothing: the imported cloud is the history's root
 }
 
 int gpmdm_pf_export(gpmdm_pf_t pf, double* states, int64_t* classes, double* ll, double* log_w,
@@ -659,7 +662,7 @@ int gpmdm_pf_set_model(gpmdm_pf_t pf, gpmdm_model_t m) {
     const std::vector<unsigned char> mask = pf->obs_mask;
     TRY(install_obs_mask(pf, mask));
   }
-  return GPMDM_OK;
+  return sm_clear(pf, ls);             // smoothing: older frames were the old model's
 }
 
 int gpmdm_pf_set_obs_cutoff(gpmdm_pf_t pf, int mode) {

@@ -1,0 +1,250 @@
+// C ABI, fixed-lag smoothing (gpmdm_pf_set_smoothing, gpmdm_pf_smoothing_depth,
+// gpmdm_pf_smoothed): the ring of per-frame {ancestors, classes, states} that every resample of
+// an enabled filter records into, and the read-out that walks it -- a clear, the trace, the
+// per-lag reduce and per lag with a pose the read-out of obs_readout.h on the traced cloud, all
+// queued on the caller's stream, then one copy-back and one wait.  Kernels: smooth.h.
+#include "capi_internal.h"
+#include "smooth.h"
+
+namespace gpmdm::capi {
+
+// the ring, and a read-out's staging of the particle rows, may take this much device memory
+constexpr size_t kSmoothBytes = (size_t)1 << 30;
+
+static size_t ring_bytes(long long P, int d, int L) {
+  return (size_t)(L + 1) * (size_t)P * (sizeof(double) * d + 2 * sizeof(int));
+}
+
+int sm_wait(gpmdm_pf* pf) {
+  if (pf->sm_pending) {
+    HIPCHK(hipEventSynchronize(pf->sm_ev));
+    pf->sm_pending = false;
+  }
+  if (pf->sm_tr_pending) {
+    HIPCHK(hipEventSynchronize(pf->sm_tr_ev));
+    pf->sm_tr_pending = false;
+  }
+  return GPMDM_OK;
+}
+
+static void launch_record(gpmdm_pf* pf, hipStream_t s) {
+  const size_t k = (size_t)pf->sm_slot() * pf->P;
+  SmRecordArgs a{};
+  a.P = pf->P;
+  a.d = pf->m->d;
+  a.ridx = pf->ridx;
+  a.cls = pf->cls;
+  a.X = pf->X;
+  a.anc_dst = pf->sm_anc + k;
+  a.cls_dst = pf->sm_cls + k;
+  a.X_dst = pf->sm_X + k * pf->m->d;
+  launch_sm_record(a, s);
+}
+
+// The frame the resample on s has just completed (pf->frame counts it already).
+int sm_record(gpmdm_pf* pf, hipStream_t s) {
+  launch_record(pf, s);
+  HIPCHK(hipGetLastError());
+  // (a frame counter that wrapped starts a new history: slots follow the counter)
+  pf->sm_depth = pf->frame == 0 ? 0 : std::min(pf->sm_L, pf->sm_depth + 1);
+  HIPCHK(hipEventRecord(pf->sm_ev, s));
+  pf->sm_pending = true;
+  pf->sm_stream = s;
+  return GPMDM_OK;
+}
+
+// Forget the history; the cloud the filter holds now is its root (no ancestors).  The caller
+// has waited for the filter's launches (quiesce, or sm_wait and the last read-out); s: the
+// lifecycle stream, synchronised here.
+int sm_clear(gpmdm_pf* pf, hipStream_t s) {
+  pf->sm_depth = 0;
+  if (pf->sm_L == 0 || !pf->initialised) return GPMDM_OK;
+  launch_record(pf, s);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(s));
+  return GPMDM_OK;
+}
+
+template <typename T>
+static int grow(T*& p, size_t& cap, size_t n, hipStream_t s) {
+  if (cap >= n) return GPMDM_OK;
+  dfree_after(p, s);                   // (after the stream's earlier work)
+  cap = 0;
+  TRY(dalloc(&p, n));
+  cap = n;
+  return GPMDM_OK;
+}
+
+}  // namespace gpmdm::capi
+
+extern "C" {
+
+int gpmdm_pf_set_smoothing(gpmdm_pf_t pf, int lag) {
+  CHECK(pf, "null handle");
+  CHECK(pf->F == 1, "smoothing serves single filters, not banks");
+  CHECK(lag >= 0 && lag <= GPMDM_SMOOTH_MAX_LAG, "lag must be in [0, GPMDM_SMOOTH_MAX_LAG]");
+  if ((pf->switched && !pf->preswitched) || pf->dyn_done || pf->propagated)
+    return fail(GPMDM_E_STATE, "set_smoothing between switch and resample");
+  gpmdm_model* m = pf->m;
+  CHECK(lag == 0 || ring_bytes(pf->P, m->d, lag) <= kSmoothBytes,
+        "the history of this lag needs more than 1 GiB of device memory ((lag + 1) x P x (d + 1) doubles)");
+  HIPCHK(hipSetDevice(m->device));
+  // a record or a read-out in flight, and the last frame's resample (it precedes the frame's
+  // read-out; a pending pre-switch reads the cloud only, and stays pending)
+  TRY(sm_wait(pf));
+  HIPCHK(pf->zslot_free());
+  dfree(pf->sm_anc);
+  dfree(pf->sm_cls);
+  dfree(pf->sm_X);
+  pf->sm_L = pf->sm_depth = 0;
+  if (lag == 0) return GPMDM_OK;
+  if (!pf->sm_ev) HIPCHK(hipEventCreateWithFlags(&pf->sm_ev, hipEventDisableTiming));
+  if (!pf->sm_tr_ev) HIPCHK(hipEventCreateWithFlags(&pf->sm_tr_ev, hipEventDisableTiming));
+  const size_t n = (size_t)(lag + 1) * pf->P;
+  if (dalloc(&pf->sm_anc, n) || dalloc(&pf->sm_cls, n) || dalloc(&pf->sm_X, n * m->d)) {
+    dfree(pf->sm_anc);
+    dfree(pf->sm_cls);
+    dfree(pf->sm_X);
+    return GPMDM_E_NOMEM;
+  }
+  pf->sm_L = lag;
+  hipStream_t ls = life_stream(m->device);
+  CHECK(ls, "the library's lifecycle stream");
+  return sm_clear(pf, ls);
+}
+
+int gpmdm_pf_smoothing_depth(gpmdm_pf_t pf, int* lag, int* depth) {
+  CHECK(pf, "null handle");
+  if (lag) *lag = pf->sm_L;
+  if (depth) *depth = pf->sm_depth;
+  return GPMDM_OK;
+}
+
+int gpmdm_pf_smoothed(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_smoothed_out* out, void* stream) {
+  CHECK(pf, "null handle");
+  CHECK(pf->F == 1, "smoothing serves single filters, not banks");
+  CHECK(pf->sm_L > 0, "smoothing is off (gpmdm_pf_set_smoothing)");
+  if (!pf->initialised) return fail(GPMDM_E_STATE, "particle filter not initialised");
+  // (a pending pre-switch reads the cloud and writes the step's tables: neither is the smoother's)
+  if ((pf->switched && !pf->preswitched) || pf->dyn_done || pf->propagated)
+    return fail(GPMDM_E_STATE, "smoothed between switch and resample");
+  CHECK(lag_first >= 0 && lag_first <= lag_last, "lags: 0 <= lag_first <= lag_last");
+  CHECK(lag_last <= pf->sm_depth, "lag_last is above the recorded depth (gpmdm_pf_smoothing_depth)");
+  gpmdm_model* m = pf->m;
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int C = m->C, d = m->d, D = m->D;
+  const long long P = pf->P;
+  const int n = lag_last - lag_first + 1;
+  const int W = C + d + 1 + 2 * D;
+  const long long nb = sm_blocks(P), ldm = sm_ld_marks(P);
+  static const gpmdm_smoothed_out none{};
+  const gpmdm_smoothed_out& o = out ? *out : none;
+  const bool obs = o.obs_mean || o.obs_spread;
+  const bool want_X = obs || o.states;
+  const size_t cnt_bytes = ((size_t)n * C * sizeof(int) + 15) & ~(size_t)15;   // counts, then the marks
+  const size_t stage = (size_t)n * ((size_t)ldm + (size_t)P * ((want_X ? sizeof(double) * d : 0) +
+                                                               (o.ancestors ? sizeof(int) : 0) +
+                                                               (o.classes ? sizeof(int) : 0)));
+  CHECK(stage <= kSmoothBytes, "these lags need more than 1 GiB of device staging (rows of P states, ancestors, "
+                               "classes and marks per lag): ask for fewer lags per call");
+  TRY(grow(pf->sm_marks, pf->sm_marks_cap, cnt_bytes + (size_t)n * ldm, s));
+  TRY(grow(pf->sm_part, pf->sm_part_cap, (size_t)n * nb * d, s));
+  if (pf->sm_out_cap < (size_t)n * W) {
+    hfree(pf->sm_pin);
+    TRY(grow(pf->sm_out, pf->sm_out_cap, (size_t)n * W, s));
+    TRY(halloc(&pf->sm_pin, (size_t)n * W, 0));
+  }
+  if (obs && !pf->sm_ro_part) TRY(dalloc(&pf->sm_ro_part, readout_part_doubles(P, D)));
+  // per-call staging of the particle rows, released in the stream's order on every exit
+  double* stage_X = nullptr;
+  int *stage_anc = nullptr, *stage_cls = nullptr;
+  int rc = GPMDM_OK;
+  if (want_X) rc = dalloc(&stage_X, (size_t)n * P * d);
+  if (rc == GPMDM_OK && o.ancestors) rc = dalloc(&stage_anc, (size_t)n * P);
+  if (rc == GPMDM_OK && o.classes) rc = dalloc(&stage_cls, (size_t)n * P);
+  std::vector<int> a32, c32;
+  auto launches = [&]() -> int {
+    // the record of the latest frame, if it ran on another stream
+    if (pf->sm_pending && pf->sm_stream != s) HIPCHK(hipStreamWaitEvent(s, pf->sm_ev, 0));
+    int* counts = reinterpret_cast<int*>(pf->sm_marks);
+    unsigned char* marks = pf->sm_marks + cnt_bytes;
+    HIPCHK(hipMemsetAsync(pf->sm_marks, 0, cnt_bytes + (size_t)n * ldm, s));
+    SmTraceArgs ta{};
+    ta.P = P;
+    ta.C = C;
+    ta.d = d;
+    ta.lag_first = lag_first;
+    ta.lag_last = lag_last;
+    ta.ring = SmRing{pf->sm_anc, pf->sm_cls, pf->sm_X, pf->sm_L + 1, pf->sm_slot()};
+    ta.counts = counts;
+    ta.partials = pf->sm_part;
+    ta.marks = marks;
+    ta.ld_marks = ldm;
+    ta.anc_out = stage_anc;
+    ta.cls_out = stage_cls;
+    ta.X_out = stage_X;
+    launch_sm_trace(ta, s);
+    SmReduceArgs ra{};
+    ra.P = P;
+    ra.C = C;
+    ra.d = d;
+    ra.nb = (int)nb;
+    ra.counts = counts;
+    ra.partials = pf->sm_part;
+    ra.marks = marks;
+    ra.ld_marks = ldm;
+    ra.out = pf->sm_out;
+    ra.ld_out = W;
+    launch_sm_reduce(ra, n, s);
+    for (int r = 0; obs && r < n; ++r) {   // each lag's pose: the read-out on its traced cloud
+      ReadoutParams rp{};
+      rp.X = stage_X + (size_t)r * P * d;
+      rp.P = P;
+      rp.d = d;
+      rp.D = D;
+      rp.ls = m->y_ls_dev;
+      rp.Xrec = m->obs.Xrec;
+      rp.nks = ksteps((int)m->N);
+      rp.Bro = m->ro_beta;
+      rp.n_groups = readout_groups(D);
+      rp.part = pf->sm_ro_part;
+      rp.out = pf->sm_out + (size_t)r * W + C + d + 1;   // {mean[D], spread[D]} of row r
+      launch_obs_readout(rp, s);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(pf->sm_pin, pf->sm_out, sizeof(double) * n * W, hipMemcpyDeviceToHost, s));
+    if (o.states) HIPCHK(hipMemcpyAsync(o.states, stage_X, sizeof(double) * n * P * d, hipMemcpyDeviceToHost, s));
+    if (o.ancestors) {
+      a32.resize((size_t)n * P);
+      HIPCHK(hipMemcpyAsync(a32.data(), stage_anc, sizeof(int) * a32.size(), hipMemcpyDeviceToHost, s));
+    }
+    if (o.classes) {
+      c32.resize((size_t)n * P);
+      HIPCHK(hipMemcpyAsync(c32.data(), stage_cls, sizeof(int) * c32.size(), hipMemcpyDeviceToHost, s));
+    }
+    return GPMDM_OK;
+  };
+  if (rc == GPMDM_OK) rc = launches();
+  pf->sm_tr_pending = hipEventRecord(pf->sm_tr_ev, s) == hipSuccess;   // (quiesce waits if the wait below fails)
+  if (stage_X) dfree_after(stage_X, s);
+  if (stage_anc) dfree_after(stage_anc, s);
+  if (stage_cls) dfree_after(stage_cls, s);
+  if (rc != GPMDM_OK) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  pf->sm_tr_pending = false;
+  if (pf->sm_pending && pf->sm_stream == s) pf->sm_pending = false;   // (the record preceded the trace on s)
+  for (int r = 0; r < n; ++r) {
+    const double* row = pf->sm_pin + (size_t)r * W;
+    if (o.class_prob) std::memcpy(o.class_prob + (size_t)r * C, row, sizeof(double) * C);
+    if (o.state_mean) std::memcpy(o.state_mean + (size_t)r * d, row + C, sizeof(double) * d);
+    if (o.distinct) o.distinct[r] = (int64_t)row[C + d];
+    if (o.obs_mean) std::memcpy(o.obs_mean + (size_t)r * D, row + C + d + 1, sizeof(double) * D);
+    if (o.obs_spread) std::memcpy(o.obs_spread + (size_t)r * D, row + C + d + 1 + D, sizeof(double) * D);
+  }
+  for (size_t i = 0; i < a32.size(); ++i) o.ancestors[i] = a32[i];
+  for (size_t i = 0; i < c32.size(); ++i) o.classes[i] = c32[i];
+  return GPMDM_OK;
+}
+
+}  // extern "C"

@@ -96,6 +96,47 @@ class Forecast:
     classes: Optional[torch.Tensor] = None              # (H, P) int64
 
 
+@dataclass
+class Smoothed:
+    """``GPMDM_PF.smoothed``'s result; row i is lag ``lags[i]``, i.e. frame ``frames[i]``."""
+    lags: torch.Tensor                                  # (n,) int64
+    frames: torch.Tensor                                # (n,) int64: frame - lag
+    class_probabilities: torch.Tensor                   # (n, C)
+    state_mean: torch.Tensor                            # (n, d)
+    distinct_ancestors: torch.Tensor                    # (n,) int64
+    observation_mean: Optional[torch.Tensor] = None     # (n, D)
+    observation_spread: Optional[torch.Tensor] = None   # (n, D)
+    ancestors: Optional[torch.Tensor] = None            # (n, P) int64
+    states: Optional[torch.Tensor] = None               # (n, P, d)
+    classes: Optional[torch.Tensor] = None              # (n, P) int64
+
+
+def _check_smoothing_lag(L) -> int:
+    if isinstance(L, bool) or not isinstance(L, (int, np.integer)):
+        raise ValueError(f"smoothing lag must be an integer, got {L!r}")
+    if not 0 <= int(L) <= _lib.GPMDM_SMOOTH_MAX_LAG:
+        raise ValueError(f"smoothing lag must be in [0, {_lib.GPMDM_SMOOTH_MAX_LAG}], got {L}")
+    return int(L)
+
+
+def _check_lag_range(lag):
+    """``smoothed``'s ``lag`` as (first, last), last None for "up to the depth"."""
+    def one(x):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 <= int(x) <= _lib.GPMDM_SMOOTH_MAX_LAG:
+            raise ValueError(f"lag must be an integer in [0, {_lib.GPMDM_SMOOTH_MAX_LAG}], got {x!r}")
+        return int(x)
+    if lag is None:
+        return 0, None
+    if isinstance(lag, (tuple, list)):
+        if len(lag) != 2:
+            raise ValueError(f"lag must be None, an integer or a pair (first, last), got {lag!r}")
+        a, b = one(lag[0]), one(lag[1])
+        if a > b:
+            raise ValueError(f"lag range must have first <= last, got {lag!r}")
+        return a, b
+    return one(lag), one(lag)
+
+
 def _as_f64_vector(z) -> np.ndarray:
     """The observation as a contiguous float64 vector (the reference casts it with
     torch.tensor(z, dtype=float64), gpmdm_pf.py:123; float32 -> float64 is exact)."""
@@ -108,7 +149,9 @@ class GPMDM_PF:
     def __init__(self, gpmdm: GPMDM, markov_switching_model, num_particles: int, *,
                  rng: str = "torch", seed=None, resample: str = "multinomial", process_group=None,
                  shard=None, exchange=None, dedup: bool = True, shard_order: bool = True,
-                 dyn_tiles: str = "auto", devices=None, obs_cutoff: bool = False, transport: str = "rccl"):
+                 dyn_tiles: str = "auto", devices=None, obs_cutoff: bool = False, transport: str = "rccl",
+                 smoothing_lag: int = 0):
+        self._smoothing_lag = _check_smoothing_lag(smoothing_lag)
         self._gpmdm = gpmdm
         self._gpmdm.set_evaluation_mode()
         self._markov_switching_model = torch.as_tensor(markov_switching_model).type(self.dtype)
@@ -180,6 +223,12 @@ class GPMDM_PF:
             _lib.check(lib.gpmdm_pf_set_dyn_tiles(h, _lib.DYN_TILES[dyn_tiles]), "dyn_tiles")
             if self._obs_cutoff:
                 _lib.check(lib.gpmdm_pf_set_obs_cutoff(h, self._obs_cutoff), "obs_cutoff")
+            if self._smoothing_lag:
+                try:
+                    _lib.check(lib.gpmdm_pf_set_smoothing(h, self._smoothing_lag), "smoothing_lag")
+                except Exception:
+                    lib.gpmdm_pf_destroy(h)     # (a history above the memory limit: no handle is left behind)
+                    raise
             return h
 
         self._peers = []                        # devices=: ranks 1.. as (handle, device index)
@@ -586,6 +635,79 @@ class GPMDM_PF:
                                                  self._stream()), "forecast")
         t = lambda a: None if a is None else torch.from_numpy(a)   # noqa: E731
         return Forecast(t(cp), t(sm), t(om), t(osp), t(st), t(cl))
+
+    def set_smoothing(self, lag: int):
+        """Keep the last ``lag`` + 1 frames' resampling ancestors, classes and states on the
+        device for ``smoothed`` (gpmdm_pf_set_smoothing; the constructor's ``smoothing_lag``).
+        Each update then records its frame with one more short launch.  ``lag=0`` turns
+        smoothing off and releases the history.  Every call, also one that repeats the lag in
+        force, clears the history: the depth is 0 and the current cloud its root; so do
+        ``reset``, ``load_state`` / ``import_state`` and a rebind to a rebuilt model
+        (``export_state`` does not carry the history).  Between updates only."""
+        L = _check_smoothing_lag(lag)
+        self._sync_model()
+        lib = _lib.load()
+        for h in [self._h] + [p[0] for p in self._peers]:
+            _lib.check(lib.gpmdm_pf_set_smoothing(h, L), "set_smoothing")
+        self._smoothing_lag = L
+
+    @property
+    def smoothing_lag(self) -> int:
+        return self._smoothing_lag
+
+    @property
+    def smoothing_depth(self) -> int:
+        """min(smoothing lag, frames recorded since the history was last cleared): the largest
+        lag ``smoothed`` serves now."""
+        if not self._smoothing_lag:
+            return 0
+        self._sync_model()                      # (a rebuilt model clears the history)
+        lag, depth = ctypes.c_int(), ctypes.c_int()
+        _lib.check(_lib.load().gpmdm_pf_smoothing_depth(self._h, ctypes.byref(lag), ctypes.byref(depth)),
+                   "smoothing_depth")
+        return depth.value
+
+    def smoothed(self, lag=None, *, observation: bool = False, particles: bool = False) -> Smoothed:
+        """What was happening ``lag`` frames ago, given what has been seen since: fixed-lag
+        smoothing from the particles' ancestry (the genealogy smoother, Kitagawa 1996;
+        gpmdm_pf_smoothed).  Each current particle p is traced back through the recorded
+        resampling indices, j_0 = p, j_{l+1} = a_{t-l}[j_l]; row l holds the class fractions
+        and the mean state of the traced cloud {X_{t-l}[j_l(p)]} (equal weights), the number
+        of distinct ancestors it rests on, with ``observation`` the pose read-out of
+        ``current_observation`` on it, and with ``particles`` the ancestors, states and
+        classes themselves.  ``lag``: None for every lag 0..``smoothing_depth``, an integer for
+        one, ``(first, last)`` for an inclusive range.
+
+        Lag 0 is the resampled cloud itself with equal weights -- not ``class_probabilities()``,
+        which pairs pre-resample weights with post-resample classes as the reference does.
+        The filter resamples every frame, so far lags hang on few ancestors (path degeneracy):
+        ``distinct_ancestors`` says how much each row is worth.  The filter is not changed: no
+        draw, no state change, and later updates are bitwise those without the call; the same
+        history gives bitwise the same result.  A sharded filter reads rank 0's history (every
+        rank records the replicated cloud).  Needs ``smoothing_lag`` / ``set_smoothing``."""
+        first, last = _check_lag_range(lag)
+        if not self._smoothing_lag:
+            raise ValueError("smoothing is off: build the filter with smoothing_lag=L or call set_smoothing(L)")
+        depth = self.smoothing_depth
+        if last is None:
+            last = depth
+        if last > depth:
+            raise ValueError(f"lag {last} is above the recorded depth {depth} (smoothing lag {self._smoothing_lag})")
+        P, C, d, D = self._num_particles, self.num_classes, self.latent_dim, self.observation_dim
+        n = last - first + 1
+        cp, sm, da = np.zeros((n, C)), np.zeros((n, d)), np.zeros(n, dtype=np.int64)
+        om = np.zeros((n, D)) if observation else None
+        osp = np.zeros((n, D)) if observation else None
+        an = np.zeros((n, P), dtype=np.int64) if particles else None
+        st = np.zeros((n, P, d)) if particles else None
+        cl = np.zeros((n, P), dtype=np.int64) if particles else None
+        out = _lib.SmoothedOut(_lib.dptr(cp), _lib.dptr(sm), _lib.i64ptr(da), _lib.dptr(om), _lib.dptr(osp),
+                               _lib.i64ptr(an), _lib.dptr(st), _lib.i64ptr(cl))
+        _lib.check(_lib.load().gpmdm_pf_smoothed(self._h, first, last, ctypes.byref(out), self._stream()),
+                   "smoothed")
+        lags = np.arange(first, last + 1, dtype=np.int64)
+        t = lambda a: None if a is None else torch.from_numpy(a)   # noqa: E731
+        return Smoothed(t(lags), t(self.frame - lags), t(cp), t(sm), t(da), t(om), t(osp), t(an), t(st), t(cl))
 
     @property
     def frame(self) -> int:

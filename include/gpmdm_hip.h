@@ -513,6 +513,58 @@ typedef struct gpmdm_forecast_out {   /* host arrays; any may be NULL */
 int gpmdm_pf_forecast(gpmdm_pf_t pf, int horizon, int mode, const uint64_t* seed,
                       const gpmdm_forecast_out* out, void* stream);
 
+/* Fixed-lag smoothing from particle ancestry: what was happening `lag` frames ago, given what has
+ * been seen since (the genealogy smoother, Kitagawa 1996, J. Comput. Graph. Stat. 5(1) §4.1).
+ * Let frame t be the last completed resample, X_t[p], c_t[p] the particles after it and
+ * a_t[p] the ancestor of slot p in frame t - 1's cloud (the resample's index,
+ * gpmdm_pf.py:206-213; gpmdm_pf_export's ridx).  With j_0(p) = p and j_{l+1}(p) =
+ * a_{t-l}[j_l(p)], particle j_l(p) of frame t - l is the lag-l ancestor of the current particle
+ * p, and row l - lag_first of each output that is not NULL holds
+ *   class_prob[c] = #{p : c_{t-l}[j_l(p)] = c} / P   (an integer count, divided once),
+ *   state_mean    = (1/P) sum_p X_{t-l}[j_l(p)]      (fixed summation order),
+ *   distinct      = the number of distinct j_l(p): P at lag 0, non-increasing in l,
+ *   obs_mean / obs_spread = gpmdm_pf_observation's mean and cloud variance of the traced cloud,
+ *   ancestors / states / classes = j_l(p), X_{t-l}[j_l(p)], c_{t-l}[j_l(p)] per current particle.
+ * Lag 0 is the resampled cloud itself with equal weights: not gpmdm_pf_read's posterior, which
+ * pairs the pre-resample weights with the post-resample classes as the reference does
+ * (gpmdm_pf.py:224-248).  Path degeneracy: the filter resamples every frame, so far lags hang on
+ * few ancestors -- `distinct` says how many each row rests on.
+ * gpmdm_pf_set_smoothing(pf, lag) keeps the last lag + 1 frames' {a, c, X} on the device (one
+ * more short launch per resample; lag 0: off, the history is released and a frame issues exactly
+ * the work it issues without smoothing); lag in [0, GPMDM_SMOOTH_MAX_LAG], GPMDM_E_INVALID when
+ * the history would take more than 1 GiB ((lag + 1) x P x (d + 1) doubles).  Between frames only
+ * (GPMDM_E_STATE inside a step); a pending pre-switch stays pending.  The history is cleared --
+ * depth 0, the current cloud its root -- by gpmdm_pf_set_smoothing (also with the lag it already
+ * has), gpmdm_pf_init, gpmdm_pf_import and gpmdm_pf_set_model; gpmdm_pf_export does not carry
+ * it.  gpmdm_pf_smoothing_depth: the lag in force and min(lag, frames recorded since the last
+ * clear), the largest lag gpmdm_pf_smoothed serves.
+ * gpmdm_pf_smoothed reads lags lag_first..lag_last (0 <= lag_first <= lag_last <= depth,
+ * GPMDM_E_INVALID otherwise or with smoothing off).  The live filter is untouched: no state
+ * change, no draw, no frame or health counter; a pending pre-switch stays pending; later frames
+ * are bitwise those without the call.  No floating-point atomics: the same history gives
+ * bitwise the same rows.  All launches are queued on `stream` without a host wait in between;
+ * the call copies the results back and synchronises `stream` once.  With obs_mean and
+ * obs_spread both NULL no observation kernel is launched.  The particle rows (and the traced
+ * clouds a pose reads) are staged on the device for the call's duration: GPMDM_E_INVALID above
+ * 1 GiB.  Between a switch and its resample: GPMDM_E_STATE.  Every rank of a sharded filter
+ * records its replicated cloud; the read-out serves the handle it is called on.  Banks:
+ * GPMDM_E_INVALID. */
+#define GPMDM_SMOOTH_MAX_LAG 4096
+typedef struct gpmdm_smoothed_out {   /* host arrays; any may be NULL; n = lag_last - lag_first + 1 */
+  double*  class_prob;   /* n x C */
+  double*  state_mean;   /* n x d */
+  int64_t* distinct;     /* n */
+  double*  obs_mean;     /* n x D */
+  double*  obs_spread;   /* n x D */
+  int64_t* ancestors;    /* n x P */
+  double*  states;       /* n x P x d */
+  int64_t* classes;      /* n x P */
+} gpmdm_smoothed_out;
+int gpmdm_pf_set_smoothing(gpmdm_pf_t pf, int lag);
+int gpmdm_pf_smoothing_depth(gpmdm_pf_t pf, int* lag, int* depth);
+int gpmdm_pf_smoothed(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_smoothed_out* out,
+                      void* stream);
+
 /* Device-side GP factor: the recipe of _precompute_kernel_inverses
  * (gpmdm.py:1284-1305) for one GP block -- the observation GP, or one class block of the
  * dynamics GP (the reference's full masked matrix has exact zeros off the class blocks):
