@@ -113,6 +113,8 @@ _SIGS = {
     "gpmdm_pf_predict": (c_int, [c_void_p, _dp, c_void_p]),
     "gpmdm_pf_set_obs_mask": (c_int, [c_void_p, c_void_p]),
     "gpmdm_pf_observation": (c_int, [c_void_p, _dp, _dp, c_void_p]),
+    "gpmdm_bank_set_obs_masks": (c_int, [c_void_p, c_void_p]),
+    "gpmdm_bank_observation": (c_int, [c_void_p, _dp, _dp, c_void_p]),
     "gpmdm_pf_forecast": (c_int, [c_void_p, c_int, c_int, POINTER(c_uint64), POINTER(ForecastOut), c_void_p]),
     "gpmdm_pf_set_smoothing": (c_int, [c_void_p, c_int]),
     "gpmdm_pf_smoothing_depth": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),

@@ -170,9 +170,47 @@ class GPMDM_PF_Bank:
         return out
 
     # ---- per-frame ------------------------------------------------------------------
-    def update(self, Z):
+    def _check_masks(self, observed):
+        """``observed`` as (F_local, D) uint8 flags (None: every dimension of every filter
+        observed).  Accepts (F, D) (each rank takes its rows, as for Z), (F_local, D) or (D,)
+        (one mask for every filter); shape errors are raised here, before the library is
+        touched."""
+        if observed is None:
+            return None
+        m = np.asarray(observed, dtype=bool)
+        F, Fl, D = self._num_filters, self.local_filters, self.observation_dim
+        if m.shape == (D,):
+            m = np.broadcast_to(m, (Fl, D))
+        elif m.shape == (F, D) and Fl != F:
+            m = m[self._f_lo:self._f_hi]
+        elif m.shape != (Fl, D):
+            raise ValueError(f"observed must be ({F}, {D}), ({Fl}, {D}) (local) or ({D},) flags, "
+                             f"got {tuple(m.shape)}")
+        return np.ascontiguousarray(m, dtype=np.uint8)
+
+    def _set_masks(self, masks):
+        """Put the masks (``_check_masks``' result) in force, if their bytes differ from the
+        ones in force (gpmdm_bank_set_obs_masks; GPMDM_PF._set_mask)."""
+        key = None if masks is None else masks.tobytes()
+        if key == getattr(self, "_mask_key", None):
+            return
+        ptr = None if masks is None else ctypes.c_void_p(masks.ctypes.data)
+        _lib.check(_lib.load().gpmdm_bank_set_obs_masks(self._h, ptr), "observed")
+        self._mask_key = key
+
+    def update(self, Z, observed=None):
         """One frame for every filter.  Z: (F, D) (all filters; each rank takes its rows)
-        or (F_local, D)."""
+        or (F_local, D).
+
+        ``observed`` (anything ``np.asarray(..., bool)`` turns into (F, D), (F_local, D) or
+        (D,) flags; default: all): the dimensions of each filter's row of ``Z`` that were seen
+        this frame, one mask per filter (``GPMDM_PF.update``'s ``observed`` for each).  Filter
+        f's particles are weighted by the reference's likelihood on the model restricted to
+        f's observed dimensions; ``Z`` elsewhere is ignored (it may be NaN).  The idiom for
+        capture streams that mark dropped markers with NaN is ``bank.update(Z,
+        observed=np.isfinite(Z))``.  A filter with no dimension observed takes a pure
+        prediction step (``w`` exactly 1/P).  ``update(Z)`` without the argument is the
+        reference's update, NaN propagation included."""
         Z = np.asarray(torch.as_tensor(Z, dtype=torch.float64).cpu().numpy(), dtype=np.float64)
         Z = Z.reshape(-1, self.observation_dim)
         if Z.shape[0] == self._num_filters and self.local_filters != self._num_filters:
@@ -180,11 +218,13 @@ class GPMDM_PF_Bank:
         if Z.shape[0] != self.local_filters:
             raise ValueError(f"expected {self._num_filters} (or {self.local_filters} local) observations, "
                              f"got {Z.shape[0]}")
+        masks = self._check_masks(observed)
         self._readout = None
         if self._h is None:
             return
         Z = np.ascontiguousarray(Z)
         self._sync_model()
+        self._set_masks(masks)
         lib, h, s = _lib.load(), self._h, self._stream()
         _lib.check(lib.gpmdm_pf_switch(h, None, None, s), "switch")
         _lib.check(lib.gpmdm_pf_propagate(h, _lib.dptr(Z), None, s), "propagate")
@@ -225,6 +265,37 @@ class GPMDM_PF_Bank:
             self._sync_model()
             _lib.check(_lib.load().gpmdm_pf_predict(self._h, _lib.dptr(out), self._stream()), "predict")
         return torch.from_numpy(out)
+
+    def current_observation(self, spread: bool = True):
+        """(F_local, D): the filtered pose of every local filter, ``GPMDM_PF.current_observation``
+        per filter -- the observation GP's mean averaged over the particles the filter holds
+        now (after masked updates: with the unseen joints imputed) and, with ``spread``, the
+        cloud's variance of each.  One pair of launches for the whole bank
+        (gpmdm_bank_observation); no state change, no draw; the same clouds give bitwise the
+        same values, and row f is bitwise a single filter's read-out of the same cloud."""
+        Fl, D = self.local_filters, self.observation_dim
+        mean = np.zeros((Fl, D))
+        var = np.zeros((Fl, D)) if spread else None
+        if self._h is not None:
+            self._sync_model()
+            _lib.check(_lib.load().gpmdm_bank_observation(self._h, _lib.dptr(mean), _lib.dptr(var), self._stream()),
+                       "current_observation")
+        if spread:
+            return torch.from_numpy(mean), torch.from_numpy(var)
+        return torch.from_numpy(mean)
+
+    def current_observation_mean(self) -> torch.Tensor:
+        """``current_observation``'s mean alone: (F_local, D)."""
+        return self.current_observation(spread=False)
+
+    def health(self, reset: bool = False) -> dict:
+        """Failure counters of the local filters together since creation (or the last reset):
+        ``GPMDM_PF.health`` (gpmdm_pf_health).  A blacked-out filter's frames add nothing."""
+        n = np.zeros(len(_lib.HEALTH), dtype=np.int64)
+        if self._h is not None:
+            _lib.check(_lib.load().gpmdm_pf_health(self._h, _lib.i64ptr(n), 1 if reset else 0, self._stream()),
+                       "health")
+        return {k: int(v) for k, v in zip(_lib.HEALTH, n)}
 
     def gather_readouts(self) -> dict:
         """All filters' read-outs on every rank (one all-gather of F x (C + d + 1))."""

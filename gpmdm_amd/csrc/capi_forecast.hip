@@ -183,6 +183,7 @@ static int launch_rollout(gpmdm_pf* pf, int H, bool mean_only, bool obs, unsigne
       ReadoutParams rp{};
       rp.X = Xnext;
       rp.P = P;
+      rp.F = 1;
       rp.d = d;
       rp.D = D;
       rp.ls = m->y_ls_dev;

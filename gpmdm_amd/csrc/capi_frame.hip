@@ -410,6 +410,9 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
   // a masked frame (gpmdm_pf_set_obs_mask): the same launches on the observed dimensions
   const bool masked = pf->masked();
   const double* lam2 = masked ? pf->lam2_obs : m->y_lam2_dev;
+  // a masked bank: lam2's row and the finish's scalars are those of each particle's filter
+  const bool fmasked = masked && pf->F > 1;
+  const long long lam_ld = fmasked ? D : 0;
   if (masked && pf->D_obs == 0) {
     // sensor blackout: a pure prediction step.  No observation kernel runs; ll is exactly 0
     // for every particle (the other ranks' entries arrive with the exchange as the same 0),
@@ -480,6 +483,7 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
       cp.S = pf->sobs;
       cp.z = zsrc;
       cp.lam2 = lam2;
+      cp.lam_ld = lam_ld;
       cp.Pf = pf->Pf;
       cp.sp_stats = auto_frame ? pf->cut_auto_dev : (pf->sp_stats_on ? pf->sp_stats : nullptr);
       // the grid's tail: equal workgroups run in whole rounds of the resident slots, so the
@@ -531,6 +535,7 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
       tp.spart = pf->sobs;
       tp.z = zsrc;
       tp.lam2 = lam2;
+      tp.lam_ld = lam_ld;
       tp.Pf = pf->Pf;
       launch_gp_tile(tp, d, false, s);
     }
@@ -554,6 +559,7 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
       oa.D = pf->D_obs;
       oa.sum_log_il2 = pf->sum_log_il2_obs;
       oa.ll_const = pf->ll_const_obs;
+      if (fmasked) oa.ftab = pf->obs_ftab();   // (the three per filter; a blacked-out filter's ll: 0)
     }
     oa.ll = pf->ll;
     oa.ll_offset = obs_lo;

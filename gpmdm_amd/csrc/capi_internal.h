@@ -306,18 +306,24 @@ struct gpmdm_pf {
   // scalars of the observed dimensions -- the likelihood of the model restricted to them.
   // z is zeroed at the unobserved positions in the staging copies (stage_z), so a NaN there
   // never reaches a kernel.
+  // A bank (gpmdm_bank_set_obs_masks) holds one mask per filter: obs_mask and lam2_obs are
+  // F x D, filter-major, the tiles read the row of each particle's filter, and the finish takes
+  // the three scalars from an F-row table {D_obs, sum_log_il2_obs, ll_const_obs} that follows
+  // lam2_obs in the same allocation (obs_ftab; one upload installs both).  D_obs is then the
+  // sum over the filters (0: every filter blacked out) and the two scalars are unused.
   std::vector<unsigned char> obs_mask;
   double* lam2_obs = nullptr;
   int D_obs = 0;
   double sum_log_il2_obs = 0.0, ll_const_obs = 0.0;
   bool masked() const { return !obs_mask.empty(); }
-  void stage_z(double* dst, const double* zh) const {   // single filters only when masked
-    const int D = m->D;
+  const double* obs_ftab() const { return lam2_obs + (size_t)F * m->D; }
+  void stage_z(double* dst, const double* zh) const {
+    const size_t n = (size_t)m->D * F;
     if (!masked()) {
-      std::memcpy(dst, zh, sizeof(double) * D * F);
+      std::memcpy(dst, zh, sizeof(double) * n);
       return;
     }
-    for (int j = 0; j < D; ++j) dst[j] = obs_mask[(size_t)j] ? zh[j] : 0.0;
+    for (size_t j = 0; j < n; ++j) dst[j] = obs_mask[j] ? zh[j] : 0.0;
   }
   // The filtered-pose read-out (gpmdm_pf_observation, obs_readout.h): the tiles' partials,
   // the device result {mean, spread} and its pinned landing buffer, allocated on first use;

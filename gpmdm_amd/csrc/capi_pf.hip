@@ -322,21 +322,35 @@ static int install_obs_mask(gpmdm_pf* pf, const std::vector<unsigned char>& mask
   // the last frame's observation kernels may still read lam2_obs: they precede its read-out
   // (a pending pre-switch reads neither, and stays pending)
   HIPCHK(pf->zslot_free());
-  if (!pf->lam2_obs) TRY(dalloc(&pf->lam2_obs, (size_t)D));
-  std::vector<double> lam2((size_t)D, 0.0);
-  int n_obs = 0;
-  double sl = 0.0;
-  for (int j = 0; j < D; ++j)
-    if (mask[(size_t)j]) {
-      lam2[(size_t)j] = 1.0 / m->y_il2[(size_t)j];   // the model's y_lam2_dev value
-      sl += std::log(m->y_il2[(size_t)j]);
-      ++n_obs;
-    }
-  TRY(h2d(pf->lam2_obs, lam2.data(), sizeof(double) * D));
+  // F rows of lam2 (a bank: one mask per filter), then the finish's F-row table of scalars
+  const int F = pf->F;
+  const size_t n_lam = (size_t)F * D, n_all = n_lam + 3 * (size_t)F;
+  if (!pf->lam2_obs) TRY(dalloc(&pf->lam2_obs, n_all));
+  std::vector<double> lam2(n_all, 0.0);
+  int n_tot = 0;
+  double sl = 0.0, lc = 0.0;
+  for (int f = 0; f < F; ++f) {
+    const unsigned char* mf = mask.data() + (size_t)f * D;
+    int n_obs = 0;
+    sl = 0.0;
+    for (int j = 0; j < D; ++j)
+      if (mf[j]) {
+        lam2[(size_t)f * D + j] = 1.0 / m->y_il2[(size_t)j];   // the model's y_lam2_dev value
+        sl += std::log(m->y_il2[(size_t)j]);
+        ++n_obs;
+      }
+    lc = (double)((float)(0.5 * n_obs) * (float)1.8378770351409912);   // capi_frame.hip weigh()
+    double* row = lam2.data() + n_lam + 3 * (size_t)f;
+    row[0] = (double)n_obs;
+    row[1] = sl;
+    row[2] = lc;
+    n_tot += n_obs;
+  }
+  TRY(h2d(pf->lam2_obs, lam2.data(), sizeof(double) * n_all));
   pf->obs_mask = mask;
-  pf->D_obs = n_obs;
-  pf->sum_log_il2_obs = sl;
-  pf->ll_const_obs = (double)((float)(0.5 * n_obs) * (float)1.8378770351409912);   // capi_frame.hip weigh()
+  pf->D_obs = n_tot;
+  pf->sum_log_il2_obs = sl;            // (single filters: the finish's arguments)
+  pf->ll_const_obs = lc;
   return GPMDM_OK;
 }
 
@@ -709,39 +723,49 @@ int gpmdm_pf_set_obs_cutoff(gpmdm_pf_t pf, int mode) {
 
 int gpmdm_pf_set_obs_mask(gpmdm_pf_t pf, const uint8_t* observed) {
   CHECK(pf, "null handle");
-  CHECK(pf->F == 1, "filter banks share one lam2 across the filters of a tile: no observation mask "
-                    "(per-filter masks are not supported)");
+  CHECK(pf->F == 1, "a filter bank takes one mask per filter, F x D flags (gpmdm_bank_set_obs_masks)");
+  return gpmdm_bank_set_obs_masks(pf, observed);
+}
+
+int gpmdm_bank_set_obs_masks(gpmdm_pf_t pf, const uint8_t* observed) {
+  CHECK(pf, "null handle");
   if ((pf->switched && !pf->preswitched) || pf->dyn_done || pf->propagated)
     return fail(GPMDM_E_STATE, "set_obs_mask between switch and resample");
   gpmdm_model* m = pf->m;
-  const int D = m->D;
+  const size_t n = (size_t)m->D * pf->F;
   if (!observed) {
     pf->obs_mask.clear();              // (lam2_obs is kept for the next mask)
     return GPMDM_OK;
   }
   HIPCHK(hipSetDevice(m->device));
-  std::vector<unsigned char> mask((size_t)D);
-  for (int j = 0; j < D; ++j) mask[(size_t)j] = observed[j] ? 1 : 0;
+  std::vector<unsigned char> mask(n);
+  for (size_t j = 0; j < n; ++j) mask[j] = observed[j] ? 1 : 0;
   return install_obs_mask(pf, mask);
 }
 
 int gpmdm_pf_observation(gpmdm_pf_t pf, double* mean, double* spread, void* stream) {
   CHECK(pf, "null handle");
-  CHECK(pf->F == 1, "the filtered-pose read-out serves single filters, not banks");
+  CHECK(pf->F == 1, "the filtered-pose read-out serves single filters, not banks (gpmdm_bank_observation)");
+  return gpmdm_bank_observation(pf, mean, spread, stream);
+}
+
+int gpmdm_bank_observation(gpmdm_pf_t pf, double* mean, double* spread, void* stream) {
+  CHECK(pf, "null handle");
   if (!pf->initialised) return fail(GPMDM_E_STATE, "particle filter not initialised");
   gpmdm_model* m = pf->m;
   HIPCHK(hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
-  const int D = m->D;
-  if (!pf->ro_part) TRY(dalloc(&pf->ro_part, readout_part_doubles(pf->P, D)));
-  if (!pf->ro_obs) TRY(dalloc(&pf->ro_obs, (size_t)2 * D));
-  if (!pf->ro_obs_pin) TRY(halloc(&pf->ro_obs_pin, (size_t)2 * D, 0));
+  const int D = m->D, F = pf->F;
+  if (!pf->ro_part) TRY(dalloc(&pf->ro_part, readout_part_doubles(pf->Pf, D, F)));
+  if (!pf->ro_obs) TRY(dalloc(&pf->ro_obs, (size_t)2 * D * F));
+  if (!pf->ro_obs_pin) TRY(halloc(&pf->ro_obs_pin, (size_t)2 * D * F, 0));
   if (!pf->ro_obs_ev) HIPCHK(hipEventCreateWithFlags(&pf->ro_obs_ev, hipEventDisableTiming));
   // the particles the filter holds now (X: written by the resample only; a pending pre-switch
   // reads it too and stays pending)
   ReadoutParams rp{};
   rp.X = pf->X;
-  rp.P = pf->P;
+  rp.P = pf->Pf;
+  rp.F = F;
   rp.d = m->d;
   rp.D = D;
   rp.ls = m->y_ls_dev;
@@ -758,10 +782,13 @@ int gpmdm_pf_observation(gpmdm_pf_t pf, double* mean, double* spread, void* stre
     pf->ro_obs_pending = true;
     return GPMDM_OK;
   }
-  HIPCHK(hipMemcpyAsync(pf->ro_obs_pin, pf->ro_obs, sizeof(double) * 2 * D, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(pf->ro_obs_pin, pf->ro_obs, sizeof(double) * 2 * D * F, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  if (mean) std::memcpy(mean, pf->ro_obs_pin, sizeof(double) * D);
-  if (spread) std::memcpy(spread, pf->ro_obs_pin + D, sizeof(double) * D);
+  for (int f = 0; f < F; ++f) {        // device rows are {mean[D], spread[D]} per filter
+    const double* row = pf->ro_obs_pin + (size_t)f * 2 * D;
+    if (mean) std::memcpy(mean + (size_t)f * D, row, sizeof(double) * D);
+    if (spread) std::memcpy(spread + (size_t)f * D, row + D, sizeof(double) * D);
+  }
   return GPMDM_OK;
 }
 

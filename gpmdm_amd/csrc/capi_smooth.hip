@@ -201,6 +201,7 @@ int gpmdm_pf_smoothed(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_sm
       ReadoutParams rp{};
       rp.X = stage_X + (size_t)r * P * d;
       rp.P = P;
+      rp.F = 1;
       rp.d = d;
       rp.D = D;
       rp.ls = m->y_ls_dev;

@@ -44,6 +44,9 @@ struct TileParams {
   const double* z;                // F x n_m
   const double* lam2;             // n_m: exp(y_log_lambdas)^2 = 1 / il2
   long long Pf;                   // particles per filter
+  // a masked bank (gpmdm_bank_set_obs_masks): lam2 is F x n_m, row pos / Pf as z; 0: one row
+  // for every filter (single filters, unmasked banks)
+  long long lam_ld;
 };
 
 void launch_gp_tile(const TileParams& p, int d, bool dyn, hipStream_t stream);
@@ -65,6 +68,7 @@ struct CutoffParams {
   double* S;                 // per position: sum_j (z_j - mu_j)^2 lam2_j
   const double* z;           // F x n_m observations
   const double* lam2;        // n_m
+  long long lam_ld;          // masked banks: lam2 is F x n_m, the particle's filter's row (0: one row)
   long long Pf;              // particles per filter
   unsigned long long* sp_stats;   // MFMA groups run / the dense kernel's, or nullptr
   // split tiles (the grid's tail): particle tiles [n_whole, n_whole + n_split) run as two

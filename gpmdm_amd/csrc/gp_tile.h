@@ -91,7 +91,11 @@ __device__ __forceinline__ double exp2_64(double t, const double* tab) {
 // instead of held in VGPRs (frees 2 d VGPRs: the 32-particle shapes above d = 12).
 // The A/B variants measured against this kernel (other exp tables, barrier cadences, wave
 // specialisation, the K* cache, ablations) live in tools/microbench/gp_tile_lab.h.
+// kTileLamRows -- the fused likelihood epilogue reads lam2 as F rows (TileParams::lam_ld), the
+// row of each particle's filter: the instantiations only a masked bank launches, so every
+// other launch runs the epilogue with one row, unchanged.
 constexpr int kTileCoordLDS = 131072;
+constexpr int kTileLamRows = 262144;
 template <int I, int E, class F>
 __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (I < E) {
@@ -104,7 +108,9 @@ template <int DI, bool DYN, int FLAGS = 0, int NW = 4, int MT = 4, int NTW = 4>
 __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const TileParams prm) {
   static_assert(MT == 1 || MT == 2 || MT == 4, "MT");
   static_assert(NTW == 4 || NTW == 6 || NTW == 8 || NTW == 16, "NTW");
-  static_assert((FLAGS & ~kTileCoordLDS) == 0, "FLAGS");
+  static_assert((FLAGS & ~(kTileCoordLDS | kTileLamRows)) == 0, "FLAGS");
+  static_assert(!DYN || !(FLAGS & kTileLamRows), "lam2 rows: the observation GP's epilogue");
+  constexpr bool LROWS = (FLAGS & kTileLamRows) != 0;
   // B fragments in flight: BR sub-steps (a full K-step, 4, for NTW <= 8; 2 for NTW = 16,
   // whose full K-step of fragments would not fit next to 128 accumulator VGPRs)
   constexpr int BR = NTW >= 16 ? 2 : 4;
@@ -461,6 +467,10 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
         // particles share one filter (always, for a single filter) reads z_j once per column.
         const int Pf = (int)prm.Pf;
         const int f0 = pos0 / Pf, f1 = (min(pos0 + PT, pos_end) - 1) / Pf;   // wave-uniform
+        // lam2's row (LROWS, a masked bank): filter f0's; a tile that mixes filters reads each
+        // particle's own filter's row, beside its z.  Otherwise the one row.
+        [[maybe_unused]] const long long lam_ld = LROWS ? prm.lam_ld : 0;
+        const double* __restrict__ lam_f0 = LROWS ? prm.lam2 + f0 * lam_ld : prm.lam2;
         double ss[MT][4];
   #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -470,7 +480,7 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
         for (int nt = 0; nt < NTW; ++nt) {
           const int jm = J * NB + 16 * (NW * nt + w) + li - coff - n_rows;
           if (jm >= 0 && jm < n_m) {
-            const double lam = prm.lam2[jm];
+            const double lam = lam_f0[jm];
             if (f0 == f1) {
               const double zj = prm.z[(long long)f0 * n_m + jm];
   #pragma unroll
@@ -487,9 +497,12 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
                 for (int r = 0; r < 4; ++r) {
                   int p = pos0 + mt * 16 + lk + 4 * r;
                   p = p < pos_end ? p : pos0;
-                  const double zz = prm.z[(long long)(p / Pf) * n_m + jm];
+                  const long long fp = p / Pf;
+                  const double zz = prm.z[fp * n_m + jm];
+                  double lp = lam;
+                  if constexpr (LROWS) lp = prm.lam2[fp * lam_ld + jm];
                   const double t = zz - acc[mt][nt][r];
-                  ss[mt][r] = fma(t * t, lam, ss[mt][r]);
+                  ss[mt][r] = fma(t * t, lp, ss[mt][r]);
                 }
             }
           }
@@ -606,6 +619,8 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
         // particles share one filter (always, for a single filter) reads z_j once per column.
         const int Pf = (int)prm.Pf;
         const int f0 = pos0 / Pf, f1 = (min(pos0 + PT, pos_end) - 1) / Pf;   // wave-uniform
+        [[maybe_unused]] const long long lam_ld = LROWS ? prm.lam_ld : 0;        // (lam2's rows: as above)
+        const double* __restrict__ lam_f0 = LROWS ? prm.lam2 + f0 * lam_ld : prm.lam2;
   #pragma unroll
         for (int h = 0; h < NH; ++h) {                          // one part at a time (registers)
           double ss[MT][4];
@@ -617,7 +632,7 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
           for (int nt = h * NTH; nt < (h + 1) * NTH; ++nt) {
             const int jm = J * NB + 16 * (NW * nt + w) + li - coff - n_rows;
             if (jm >= 0 && jm < n_m) {
-              const double lam = prm.lam2[jm];
+              const double lam = lam_f0[jm];
               if (f0 == f1) {
                 const double zj = prm.z[(long long)f0 * n_m + jm];
   #pragma unroll
@@ -634,9 +649,12 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
                   for (int r = 0; r < 4; ++r) {
                     int p = pos0 + mt * 16 + lk + 4 * r;
                     p = p < pos_end ? p : pos0;
-                    const double zz = prm.z[(long long)(p / Pf) * n_m + jm];
+                    const long long fp = p / Pf;
+                    const double zz = prm.z[fp * n_m + jm];
+                    double lp = lam;
+                    if constexpr (LROWS) lp = prm.lam2[fp * lam_ld + jm];
                     const double t = zz - acc[mt][nt][r];
-                    ss[mt][r] = fma(t * t, lam, ss[mt][r]);
+                    ss[mt][r] = fma(t * t, lp, ss[mt][r]);
                   }
               }
             }
@@ -718,6 +736,26 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
   }
 }
 
+// The observation GP's shapes; EF: epilogue flags (kTileLamRows or 0).
+template <int DI, int EF>
+void launch_obs_d(const TileParams& p, dim3 grid, hipStream_t stream) {
+  const TileGeo g = p.geo;
+  constexpr int kCoordVar = DI > 12 ? kTileCoordLDS : 0;   // (launch_d)
+  if (g.mt == 2) {
+    hipLaunchKernelGGL((k_gp_tile<DI, false, kCoordVar | EF, 4, 2, 8>), grid, dim3(256), 0, stream, p);
+  } else if (g.mt == 1 && g.ntw == 8) {
+    // 16-row tiles over the 32 x 512 image (small filters, capi_model.hip obs_pick; d <= 12)
+    if constexpr (DI <= 12) hipLaunchKernelGGL((k_gp_tile<DI, false, EF, 4, 1, 8>), grid, dim3(256), 0, stream, p);
+  } else if (g.mt == 1 && g.ntw == 4) {
+    // the 16 x 256 image of small models and filters (capi_model.hip obs_pick; d <= 12)
+    if constexpr (DI <= 12) hipLaunchKernelGGL((k_gp_tile<DI, false, EF, 4, 1, 4>), grid, dim3(256), 0, stream, p);
+  } else if (g.nw == 8) {
+    hipLaunchKernelGGL((k_gp_tile<DI, false, EF, 8>), grid, dim3(512), 0, stream, p);
+  } else {
+    hipLaunchKernelGGL((k_gp_tile<DI, false, EF, 4>), grid, dim3(256), 0, stream, p);
+  }
+}
+
 template <int DI>
 void launch_d(const TileParams& p, bool dyn, hipStream_t stream) {
   const dim3 grid((unsigned)(p.n_j_max * p.tiles_ub));
@@ -738,18 +776,10 @@ void launch_d(const TileParams& p, bool dyn, hipStream_t stream) {
       hipLaunchKernelGGL((k_gp_tile<DI, true, 0, 4, 1, 4>), grid, dim3(256), 0, stream, p);
     else
       hipLaunchKernelGGL((k_gp_tile<DI, true, 0, 4>), grid, dim3(256), 0, stream, p);
-  } else if (g.mt == 2) {
-    hipLaunchKernelGGL((k_gp_tile<DI, false, kCoordVar, 4, 2, 8>), grid, dim3(256), 0, stream, p);
-  } else if (g.mt == 1 && g.ntw == 8) {
-    // 16-row tiles over the 32 x 512 image (small filters, capi_model.hip obs_pick; d <= 12)
-    if constexpr (DI <= 12) hipLaunchKernelGGL((k_gp_tile<DI, false, 0, 4, 1, 8>), grid, dim3(256), 0, stream, p);
-  } else if (g.mt == 1 && g.ntw == 4) {
-    // the 16 x 256 image of small models and filters (capi_model.hip obs_pick; d <= 12)
-    if constexpr (DI <= 12) hipLaunchKernelGGL((k_gp_tile<DI, false, 0, 4, 1, 4>), grid, dim3(256), 0, stream, p);
-  } else if (g.nw == 8) {
-    hipLaunchKernelGGL((k_gp_tile<DI, false, 0, 8>), grid, dim3(512), 0, stream, p);
+  } else if (p.lam_ld) {
+    launch_obs_d<DI, kTileLamRows>(p, grid, stream);   // a masked bank: lam2 per filter
   } else {
-    hipLaunchKernelGGL((k_gp_tile<DI, false, 0, 4>), grid, dim3(256), 0, stream, p);
+    launch_obs_d<DI, 0>(p, grid, stream);
   }
 }
 

@@ -55,7 +55,9 @@ __device__ __forceinline__ double row16_sum(double v) {
   return v;
 }
 
-template <int DI, int NW, int MT, int NTW>
+// LROWS: lam2 is F rows (CutoffParams::lam_ld), the row of each particle's filter -- the
+// instantiations only a masked bank launches; every other launch reads the one row, unchanged.
+template <int DI, int NW, int MT, int NTW, bool LROWS = false>
 __global__ __launch_bounds__(64 * NW, 2) void k_obs_cutoff(const CutoffParams prm) {
   static_assert(NTW <= 8, "a full K-step of B fragments per tile in registers");
   // the generation reads the particle coordinates from LDS instead of VGPRs from d = 4: the
@@ -432,13 +434,16 @@ __global__ __launch_bounds__(64 * NW, 2) void k_obs_cutoff(const CutoffParams pr
         const int jm = 16 * (i2 - n_act) + li;
         const bool real = jm < prm.n_m;
         const double lam = real ? prm.lam2[jm] : 0.0;
+        [[maybe_unused]] const long long lam_ld = LROWS && real ? prm.lam_ld : 0;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int pr = mt * 16 + lk + 4 * r;
             const double t = real ? prm.z[pfil[pr] * prm.n_m + jm] - acc[mt][nt][r] : 0.0;
-            const double v = row16_sum((t * t) * lam);
+            double lp = lam;
+            if constexpr (LROWS) lp = real ? prm.lam2[pfil[pr] * lam_ld + jm] : 0.0;   // its filter's row
+            const double v = row16_sum((t * t) * lp);
             if (li == 0) ptile[(NW * nt + w) * PT + pr] = v;
           }
       }
@@ -497,10 +502,17 @@ bool launch_cut_d(const CutoffParams& p, hipStream_t s) {
   if (p.chunk_grid && (p.n_whole != 0 || p.n_split <= 0 || p.n_chunk_max <= 0 ||
                        (long long)p.n_chunk_max * cutoff_tile_list_chunk() < p.T_R + p.T_M))
     return false;
-  if constexpr (DI <= 8)
-    hipLaunchKernelGGL((k_obs_cutoff<DI, 4, 2, 8>), dim3(grid), dim3(256), 0, s, p);
-  else
-    hipLaunchKernelGGL((k_obs_cutoff<DI, 8, 4, 4>), dim3(grid), dim3(512), 0, s, p);
+  if constexpr (DI <= 8) {
+    if (p.lam_ld)
+      hipLaunchKernelGGL((k_obs_cutoff<DI, 4, 2, 8, true>), dim3(grid), dim3(256), 0, s, p);
+    else
+      hipLaunchKernelGGL((k_obs_cutoff<DI, 4, 2, 8>), dim3(grid), dim3(256), 0, s, p);
+  } else {
+    if (p.lam_ld)
+      hipLaunchKernelGGL((k_obs_cutoff<DI, 8, 4, 4, true>), dim3(grid), dim3(512), 0, s, p);
+    else
+      hipLaunchKernelGGL((k_obs_cutoff<DI, 8, 4, 4>), dim3(grid), dim3(512), 0, s, p);
+  }
   return true;
 }
 

@@ -28,6 +28,9 @@
 // tiles per column, then the 16 runs in order), so the spread is never formed as
 // E[mu^2] - mean^2 and every reduction has a fixed order: the same cloud gives bitwise the
 // same read-out on every call.
+// A bank (gpmdm_bank_observation) adds a filter dimension to both grids: ceil(P / 64) tiles per
+// filter, cut within the filter, partials and finish per filter -- the partition within a filter
+// is the single filter's, so row f is bitwise the read-out of a single filter holding f's cloud.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,22 +44,23 @@ constexpr int kRoPT = 64;        // particles per workgroup
 constexpr int kRoGC = 64;        // columns per group (4 waves x one 16-column tile)
 
 struct ReadoutParams {
-  const double* X;               // P x d particle states
-  long long P;
+  const double* X;               // F x P x d particle states
+  long long P;                   // particles per filter
+  int F;                         // filters (a bank: one pair of launches for all; 0 or 1: one cloud)
   int d, D;
   const double* ls;              // d observation-kernel lengthscales (device)
   const double* Xrec;            // the observation image's row records
   int nks;                       // K-steps: ksteps(N)
   const double* Bro;             // fragment-ordered beta (pack_readout_beta)
   int n_groups;                  // column groups: ceil(D / 64)
-  double* part;                  // n_tiles x {mean, M2} x (64 n_groups)
-  double* out;                   // {mean[D], spread[D]}
+  double* part;                  // F x n_tiles x {mean, M2} x (64 n_groups)
+  double* out;                   // F x {mean[D], spread[D]}
 };
 
 inline int readout_tiles(long long P) { return (int)((P + kRoPT - 1) / kRoPT); }
 inline int readout_groups(int D) { return (D + kRoGC - 1) / kRoGC; }
-inline size_t readout_part_doubles(long long P, int D) {
-  return (size_t)readout_tiles(P) * readout_groups(D) * kRoGC * 2;
+inline size_t readout_part_doubles(long long P, int D, int F = 1) {
+  return (size_t)F * readout_tiles(P) * readout_groups(D) * kRoGC * 2;
 }
 
 // beta (N x D row-major) in the kernel's fragment order: readout_groups(D) * ksteps(N) * 1024 doubles

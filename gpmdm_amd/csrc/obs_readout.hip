@@ -31,6 +31,7 @@ __global__ __launch_bounds__(256) void k_obs_readout(const ReadoutParams prm) {
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tile = blockIdx.x, G = blockIdx.y;
+  const long long fil = blockIdx.z;                          // the filter (a bank: tiles are cut within it)
   const long long pos0 = (long long)tile * kRoPT;
   const int d = prm.d, RW = d + 1, nks = prm.nks;
 
@@ -42,7 +43,7 @@ __global__ __launch_bounds__(256) void k_obs_readout(const ReadoutParams prm) {
   if (pos >= prm.P) pos = pos0;                              // padded row: count 0 in the epilogue
   double asq = 0.0;
   for (int j = 0; j < d; ++j) {
-    const double xs = prm.X[pos * d + j] / prm.ls[j];
+    const double xs = prm.X[(fil * prm.P + pos) * d + j] / prm.ls[j];
     asq = fma(xs, xs, asq);
     if ((j & 3) == w) PA[j][m] = (2.0 * kScale) * xs;
   }
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void k_obs_readout(const ReadoutParams prm) {
     const int Dpad = prm.n_groups * kRoGC;
     // two planes per tile, so each value is an 8-byte store of its own (no 16-byte VGPR
     // stores in this code base: tests/test_isa_guard.py)
-    double* o = prm.part + (size_t)tile * 2 * Dpad + kRoGC * G + 16 * w + li;
+    double* o = prm.part + ((size_t)fil * gridDim.x + tile) * 2 * Dpad + kRoGC * G + 16 * w + li;
     o[0] = mean;
     o[Dpad] = m2;
   }
@@ -138,19 +139,20 @@ __device__ __forceinline__ void chan_merge(double& n, double& mean, double& M2, 
 }
 
 // 16 columns x 16 runs of tiles per workgroup: run r merges its contiguous tiles in order,
-// then the runs are merged in order.
+// then the runs are merged in order.  blockIdx.y: the filter, over its own n_tiles partials.
 __global__ __launch_bounds__(256) void k_obs_readout_finish(const ReadoutParams prm, int n_tiles) {
   __shared__ double sn[16][16], sm[16][16], sq[16][16];
   const int cl = threadIdx.x & 15, run = threadIdx.x >> 4;
   const int Dpad = prm.n_groups * kRoGC;
   const int col = blockIdx.x * 16 + cl;                      // < Dpad (a multiple of 16)
+  const long long fil = blockIdx.y;
   const int chunk = (n_tiles + 15) / 16;
   const int t0 = run * chunk, t1 = min(n_tiles, t0 + chunk);
   double n = 0.0, mean = 0.0, M2 = 0.0;
   for (int t = t0; t < t1; ++t) {
     const long long left = prm.P - (long long)t * kRoPT;
     const double nb = left < kRoPT ? (double)left : (double)kRoPT;
-    const double* p = prm.part + (size_t)t * 2 * Dpad + col;
+    const double* p = prm.part + ((size_t)fil * n_tiles + t) * 2 * Dpad + col;
     chan_merge(n, mean, M2, nb, p[0], p[Dpad]);
   }
   sn[run][cl] = n;
@@ -159,15 +161,17 @@ __global__ __launch_bounds__(256) void k_obs_readout_finish(const ReadoutParams 
   __syncthreads();
   if (run == 0 && col < prm.D) {
     for (int r = 1; r < 16; ++r) chan_merge(n, mean, M2, sn[r][cl], sm[r][cl], sq[r][cl]);
-    prm.out[col] = mean;
-    prm.out[prm.D + col] = M2 / n;
+    double* out = prm.out + fil * 2 * prm.D;
+    out[col] = mean;
+    out[prm.D + col] = M2 / n;
   }
 }
 
 void launch_obs_readout(const ReadoutParams& p, hipStream_t s) {
   const int tiles = readout_tiles(p.P);
-  hipLaunchKernelGGL(k_obs_readout, dim3(tiles, p.n_groups), dim3(256), 0, s, p);
-  hipLaunchKernelGGL(k_obs_readout_finish, dim3(p.n_groups * kRoGC / 16), dim3(256), 0, s, p, tiles);
+  const int F = p.F > 0 ? p.F : 1;                           // (a zero-initialised F: one cloud)
+  hipLaunchKernelGGL(k_obs_readout, dim3(tiles, p.n_groups, F), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(k_obs_readout_finish, dim3(p.n_groups * kRoGC / 16, F), dim3(256), 0, s, p, tiles);
 }
 
 }  // namespace gpmdm

@@ -169,6 +169,11 @@ struct ObsFinishArgs {
   const double* spart;            // [J][ld_q] for J in [jm0, n_j), or nullptr
   int jm0, n_j;
   double sum_log_il2;             // sum_j log il2_j
+  // a masked bank (gpmdm_bank_set_obs_masks): row f = {D_obs, sum_log_il2_obs, ll_const_obs} of
+  // filter f replaces D, sum_log_il2 and ll_const for the outputs of f's particles (the
+  // particle an output belongs to, through own, over Pf); a row with D_obs = 0 is a blackout:
+  // ll exactly 0.  nullptr: the three arguments serve every output.
+  const double* ftab;
   unsigned* health;               // kHealth* counters (PF) or nullptr
   // single filters: the maximum of each block's ll (ord_enc keys), which the normaliser
   // reads instead of running k_norm_max (nullptr: not produced)

@@ -714,6 +714,21 @@ __global__ __launch_bounds__(kB) void k_obs_finish(ObsFinishArgs a) {
 // (the reference's double count of log var kept, gpmdm_pf.py:188-192).
 // (a device function: k_small_resample computes a deferred finish with the same code)
 __device__ __forceinline__ double obs_ll_value(const ObsFinishArgs& a, long long o, double& vc) {
+  double Dn = a.D, sum_log_il2 = a.sum_log_il2, ll_const = a.ll_const;
+  if (a.ftab) {
+    // a masked bank: the three scalars of the filter that owns this output's particle
+    const long long pi = a.own ? a.own[a.ll_offset + o] : a.ll_offset + o;
+    const double* row = a.ftab + 3 * (pi / a.Pf);
+    Dn = row[0];
+    sum_log_il2 = row[1];
+    ll_const = row[2];
+    if (Dn == 0.0) {
+      // blackout: ll is exactly 0 whatever the tiles left (0 * log(vc) is NaN for vc <= 0),
+      // and nothing for the health counters
+      vc = 1.0;
+      return 0.0;
+    }
+  }
   double q = 0.0;
   for (int k = 0; k < a.n_parts; ++k) q += a.qpart[(long long)k * a.ld_q + o];
   double S = 0.0;
@@ -749,7 +764,7 @@ __device__ __forceinline__ double obs_ll_value(const ObsFinishArgs& a, long long
     }
   }
   vc = 1.0 - q;                                        // k(x*,x*) = 1 (gpmdm.py:991)
-  return -0.5 * S / vc - a.D * log(vc) - a.sum_log_il2 - a.ll_const;
+  return -0.5 * S / vc - Dn * log(vc) - sum_log_il2 - ll_const;
 }
 
 __global__ __launch_bounds__(kB) void k_obs_ll(ObsFinishArgs a) {

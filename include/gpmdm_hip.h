@@ -453,8 +453,23 @@ int gpmdm_pf_predict(gpmdm_pf_t pf, double* mean, void* stream);
  * step: no observation kernel runs, ll is exactly 0 and w exactly 1/P.  gpmdm_pf_step,
  * gpmdm_pf_propagate and gpmdm_pf_weigh honour it; every rank of a sharded filter must hold
  * the same mask (gpmdm_pf_propagate_multi: GPMDM_E_INVALID otherwise).  Filter banks:
- * GPMDM_E_INVALID (their filters share one lambda^2 per tile). */
+ * GPMDM_E_INVALID (one mask per filter: gpmdm_bank_set_obs_masks). */
 int gpmdm_pf_set_obs_mask(gpmdm_pf_t pf, const uint8_t* observed);
+
+/* One mask per filter of a bank, gpmdm_pf_set_obs_mask's semantics for each: the mask holds
+ * until changed, is set between frames only (GPMDM_E_STATE inside a step), leaves a pending
+ * pre-switch pending, is re-derived when the handle is rebound to a rebuilt model, and is not
+ * carried by export / import.  Filter f's frame computes the reference's likelihood on the
+ * model restricted to f's observed dimensions: the device holds lambda^2 as F x D (0 at f's
+ * unobserved dimensions) and an F-row table of D_obs, sum log il2 and the float32 constant;
+ * the observation tiles read the row of each particle's own filter (a tile may mix filters)
+ * and the likelihood finish the table row of the filter that owns the output's particle.
+ * Each filter's row of z is zeroed at that filter's unobserved positions in the staging copy.
+ * A filter with no dimension observed gets ll exactly 0 and w exactly 1/P and adds nothing to
+ * the health counters; when every filter is blacked out no observation kernel runs.  The
+ * install waits for the handle's own previous frame only, never for the device.  Any handle:
+ * on a single filter (F = 1) this is gpmdm_pf_set_obs_mask. */
+int gpmdm_bank_set_obs_masks(gpmdm_pf_t pf, const uint8_t* observed);   /* F x D bytes, filter-major; NULL: all observed */
 
 /* The filtered pose: the observation-space read-out of the particles the filter holds now
  * (post-resample, equal weights):
@@ -466,8 +481,15 @@ int gpmdm_pf_set_obs_mask(gpmdm_pf_t pf, const uint8_t* observed);
  * import.  A mean-only GP tile of its own (csrc/obs_readout.h); fixed-order reductions, so
  * the same cloud gives bitwise the same values on every call.  A sharded filter evaluates
  * its replicated cloud on the handle it is called on.  Synchronises `stream`; with mean and
- * spread both NULL the kernels are launched only (timing).  Banks: GPMDM_E_INVALID. */
+ * spread both NULL the kernels are launched only (timing).  Banks: GPMDM_E_INVALID
+ * (gpmdm_bank_observation). */
 int gpmdm_pf_observation(gpmdm_pf_t pf, double* mean, double* spread, void* stream);
+
+/* The filtered pose of every filter of a bank: row f of mean / spread is gpmdm_pf_observation
+ * of filter f's cloud, bitwise (tiles are cut within a filter, ceil(P / 64) per filter, and
+ * partials and finish run per filter), in one pair of launches for the whole bank.  Any
+ * handle: on a single filter (F = 1) this is gpmdm_pf_observation. */
+int gpmdm_bank_observation(gpmdm_pf_t pf, double* mean, double* spread, void* stream);   /* F x D each, filter-major; spread may be NULL */
 
 /* Multi-step forecast: class, latent state and pose h = 1..horizon frames ahead.  Starting from
  * the particles the filter holds now (post-resample, equal weights), a scratch copy of the
