@@ -119,6 +119,9 @@ _SIGS = {
     "gpmdm_pf_set_smoothing": (c_int, [c_void_p, c_int]),
     "gpmdm_pf_smoothing_depth": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
     "gpmdm_pf_smoothed": (c_int, [c_void_p, c_int, c_int, POINTER(SmoothedOut), c_void_p]),
+    "gpmdm_bank_forecast": (c_int, [c_void_p, c_int, c_int, POINTER(c_uint64), POINTER(ForecastOut), c_void_p]),
+    "gpmdm_bank_set_smoothing": (c_int, [c_void_p, c_int]),
+    "gpmdm_bank_smoothed": (c_int, [c_void_p, c_int, c_int, POINTER(SmoothedOut), c_void_p]),
     "gpmdm_pf_set_comm": (c_int, [c_void_p, c_void_p, c_int]),
     "gpmdm_comm_unique_id": (c_int, [c_void_p]),
     "gpmdm_comm_init": (c_int, [c_int, c_int, c_void_p, c_int, POINTER(c_void_p)]),

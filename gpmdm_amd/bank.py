@@ -28,12 +28,18 @@ import torch
 from . import _lib, replay
 from .distributed import shard_range
 from .model import GPMDM
+from .pf import Forecast, Smoothed, _check_lag_range, _check_smoothing_lag
+
+
+def _filter_major(a):
+    """A (steps, F, ...) result of the library as a contiguous (F, steps, ...) tensor."""
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(np.swapaxes(a, 0, 1)))
 
 
 class GPMDM_PF_Bank:
     def __init__(self, gpmdm: GPMDM, markov_switching_model, num_filters: int, num_particles: int, *,
                  seed=None, resample: str = "multinomial", process_group=None, shard=None,
-                 dedup: bool = True, dyn_tiles: str = "auto", obs_cutoff: bool = False):
+                 dedup: bool = True, dyn_tiles: str = "auto", obs_cutoff: bool = False, smoothing_lag: int = 0):
         self._gpmdm = gpmdm
         self._gpmdm.set_evaluation_mode()
         self._T = torch.as_tensor(markov_switching_model).type(torch.float64)
@@ -41,6 +47,7 @@ class GPMDM_PF_Bank:
             raise ValueError("Number of classes in the GPMDM model and the Markov model do not match")
         if resample not in ("multinomial", "systematic"):
             raise ValueError("resample must be 'multinomial' or 'systematic'")
+        self._smoothing_lag = _check_smoothing_lag(smoothing_lag)
         self._num_filters = int(num_filters)
         self._num_particles = int(num_particles)
         if self._num_filters < 1 or self._num_particles < 1:
@@ -84,6 +91,8 @@ class GPMDM_PF_Bank:
             if obs_cutoff:                    # the observation GP's kernel-value cutoff (GPMDM_PF's)
                 _lib.check(_lib.load().gpmdm_pf_set_obs_cutoff(h, 1), "obs_cutoff")
             self._init_particles()
+            if self._smoothing_lag:
+                self.set_smoothing(self._smoothing_lag)
 
     def __del__(self):
         try:
@@ -287,6 +296,110 @@ class GPMDM_PF_Bank:
     def current_observation_mean(self) -> torch.Tensor:
         """``current_observation``'s mean alone: (F_local, D)."""
         return self.current_observation(spread=False)
+
+    def forecast(self, horizon: int, *, mode: str = "sample", observation: bool = True,
+                 particles: bool = False, seed=None) -> Forecast:
+        """``GPMDM_PF.forecast`` for every local filter in one sequence of launches
+        (gpmdm_bank_forecast): the grouping and the dynamics tiles run once over all F x P
+        particles, counts, sums and the pose read-out per filter.  Every field has a leading
+        filter axis: ``class_probabilities`` (F_local, H, C), ``state_mean`` (F_local, H, d),
+        the pose (F_local, H, D), with ``particles`` ``states`` (F_local, H, P, d) and
+        ``classes`` (F_local, H, P).
+
+        Filter f draws with the key ``seed + f`` (default: the bank's seed, i.e. the filter's
+        own key) and its in-filter particle index, so row f is bitwise
+        ``GPMDM_PF.forecast(horizon, seed=seed + f)`` of a single filter holding f's cloud at
+        the same frame -- except ``state_mean``, which a bank sums per filter in particle order
+        (the single filter sums in class-grouped order): the same mean to rounding, bitwise
+        reproducible, independent of ``horizon`` and identical between a full bank and the
+        shards of a sharded one.  The bank is not changed by the call."""
+        if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)):
+            raise ValueError(f"horizon must be an integer, got {horizon!r}")
+        H = int(horizon)
+        if not 1 <= H <= _lib.GPMDM_FORECAST_MAX_HORIZON:
+            raise ValueError(f"horizon must be in [1, {_lib.GPMDM_FORECAST_MAX_HORIZON}], got {H}")
+        if mode not in _lib.FORECAST_MODES:
+            raise ValueError(f"mode must be one of {sorted(_lib.FORECAST_MODES)}, got {mode!r}")
+        Fl, P, C, d, D = self.local_filters, self._num_particles, self.num_classes, self.latent_dim, self.observation_dim
+        # the library's layout: step-major, then filter-major
+        cp, sm = np.zeros((H, Fl, C)), np.zeros((H, Fl, d))
+        om = np.zeros((H, Fl, D)) if observation else None
+        osp = np.zeros((H, Fl, D)) if observation else None
+        st = np.zeros((H, Fl, P, d)) if particles else None
+        cl = np.zeros((H, Fl, P), dtype=np.int64) if particles else None
+        if self._h is not None:
+            self._sync_model()
+            out = _lib.ForecastOut(_lib.dptr(cp), _lib.dptr(sm), _lib.dptr(om), _lib.dptr(osp), _lib.dptr(st),
+                                   _lib.i64ptr(cl))
+            # (the handle's filter 0 is the bank's filter f_lo)
+            sd = None if seed is None else ctypes.byref(ctypes.c_uint64((int(seed) + self._f_lo) & (2 ** 64 - 1)))
+            _lib.check(_lib.load().gpmdm_bank_forecast(self._h, H, _lib.FORECAST_MODES[mode], sd, ctypes.byref(out),
+                                                       self._stream()), "forecast")
+        return Forecast(*(_filter_major(a) for a in (cp, sm, om, osp, st, cl)))
+
+    def set_smoothing(self, lag: int):
+        """``GPMDM_PF.set_smoothing`` for the bank (gpmdm_bank_set_smoothing): keep the last
+        ``lag`` + 1 frames' ancestors, classes and states of every filter on the device; each
+        update then records its frame with one more short launch.  ``lag=0`` turns smoothing
+        off and releases the history (the bank then issues exactly the launches of a bank built
+        without it).  Every call clears the history, as do ``reset``, ``load_state`` /
+        ``import_state`` and a rebind to a rebuilt model; ``export_state`` does not carry it.
+        Between updates only."""
+        L = _check_smoothing_lag(lag)
+        if self._h is not None:
+            self._sync_model()
+            _lib.check(_lib.load().gpmdm_bank_set_smoothing(self._h, L), "set_smoothing")
+        self._smoothing_lag = L
+
+    @property
+    def smoothing_lag(self) -> int:
+        return self._smoothing_lag
+
+    @property
+    def smoothing_depth(self) -> int:
+        """min(smoothing lag, frames recorded since the history was last cleared): the largest
+        lag ``smoothed`` serves now (every filter of the bank steps together)."""
+        if not self._smoothing_lag or self._h is None:
+            return 0
+        self._sync_model()                      # (a rebuilt model clears the history)
+        lag, depth = ctypes.c_int(), ctypes.c_int()
+        _lib.check(_lib.load().gpmdm_pf_smoothing_depth(self._h, ctypes.byref(lag), ctypes.byref(depth)),
+                   "smoothing_depth")
+        return depth.value
+
+    def smoothed(self, lag=None, *, observation: bool = False, particles: bool = False) -> Smoothed:
+        """``GPMDM_PF.smoothed`` for every local filter in one trace (gpmdm_bank_smoothed):
+        each filter's current particles are traced back through its own recorded ancestors.
+        ``lags`` and ``frames`` stay (n,); every other field has a leading filter axis --
+        ``class_probabilities`` (F_local, n, C), ``state_mean`` (F_local, n, d),
+        ``distinct_ancestors`` (F_local, n), the pose (F_local, n, D), with ``particles``
+        ``ancestors`` (in-filter indices) and ``classes`` (F_local, n, P) and ``states``
+        (F_local, n, P, d).  Row f is bitwise ``GPMDM_PF.smoothed`` of a single filter with the
+        same history, ``state_mean`` included.  The bank is not changed by the call."""
+        first, last = _check_lag_range(lag)
+        if not self._smoothing_lag:
+            raise ValueError("smoothing is off: build the bank with smoothing_lag=L or call set_smoothing(L)")
+        depth = self.smoothing_depth
+        if last is None:
+            last = depth
+        if last > depth:
+            raise ValueError(f"lag {last} is above the recorded depth {depth} (smoothing lag {self._smoothing_lag})")
+        Fl, P, C, d, D = self.local_filters, self._num_particles, self.num_classes, self.latent_dim, self.observation_dim
+        n = last - first + 1
+        cp, sm, da = np.zeros((n, Fl, C)), np.zeros((n, Fl, d)), np.zeros((n, Fl), dtype=np.int64)
+        om = np.zeros((n, Fl, D)) if observation else None
+        osp = np.zeros((n, Fl, D)) if observation else None
+        an = np.zeros((n, Fl, P), dtype=np.int64) if particles else None
+        st = np.zeros((n, Fl, P, d)) if particles else None
+        cl = np.zeros((n, Fl, P), dtype=np.int64) if particles else None
+        if self._h is not None:
+            out = _lib.SmoothedOut(_lib.dptr(cp), _lib.dptr(sm), _lib.i64ptr(da), _lib.dptr(om), _lib.dptr(osp),
+                                   _lib.i64ptr(an), _lib.dptr(st), _lib.i64ptr(cl))
+            _lib.check(_lib.load().gpmdm_bank_smoothed(self._h, first, last, ctypes.byref(out), self._stream()),
+                       "smoothed")
+        lags = np.arange(first, last + 1, dtype=np.int64)
+        return Smoothed(torch.from_numpy(lags), torch.from_numpy(self.frame - lags),
+                        *(_filter_major(a) for a in (cp, sm, da, om, osp, an, st, cl)))
 
     def health(self, reset: bool = False) -> dict:
         """Failure counters of the local filters together since creation (or the last reset):

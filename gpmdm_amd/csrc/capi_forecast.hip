@@ -8,20 +8,6 @@
 
 namespace gpmdm::capi {
 
-// staging of the per-step clouds may take this much device memory (H x P x (d + 1) doubles)
-constexpr size_t kForecastStageBytes = (size_t)1 << 30;
-
-// the forecast's class tables: the layout of gpmdm_pf::small's (class_start, counts, segments)
-struct FcTables {
-  int* t;
-  int* class_start() const { return t; }
-  int* counts() const { return t + 40; }
-  int* seg_begin() const { return t + 80; }
-  int* seg_end() const { return t + 120; }
-  int* seg_out() const { return t + 160; }
-  int* seg_tiles() const { return t + 200; }
-};
-
 static int ensure_scratch(gpmdm_pf* pf, int H, bool obs) {
   const gpmdm_model* m = pf->m;
   const int C = m->C, d = m->d, D = m->D;
@@ -60,6 +46,74 @@ static int ensure_scratch(gpmdm_pf* pf, int H, bool obs) {
   return GPMDM_OK;
 }
 
+// The filter's grouping passes on the forecast's own tables: classes `cls` (all pf->P particles,
+// a bank's F x Pf among them), whose per-block counts are in fc_blockcounts.
+void fc_group(gpmdm_pf* pf, const int* cls, hipStream_t s) {
+  const gpmdm_model* m = pf->m;
+  const long long P = pf->P;
+  const FcTables tb{pf->fc_tab};
+  ScanArgs sc{};
+  sc.nb = (int)cdiv(P, 256);
+  sc.C = m->C;
+  sc.pt = m->dyn_set(true)[0].geo.pt();
+  sc.lo = 0;
+  sc.hi = P;
+  sc.blockcounts = pf->fc_blockcounts;
+  sc.cls_new = cls;
+  sc.blockoff = pf->fc_blockoff;
+  sc.class_start = tb.class_start();
+  sc.counts = tb.counts();
+  sc.seg_pos_begin = tb.seg_begin();
+  sc.seg_pos_end = tb.seg_end();
+  sc.seg_out_base = tb.seg_out();
+  sc.seg_tile_start = tb.seg_tiles();
+  launch_scan_counts(sc, s);
+  GroupArgs ga{};
+  ga.P = P;
+  ga.n = P;
+  ga.C = m->C;
+  ga.cls_new = cls;
+  ga.class_start = tb.class_start();
+  ga.blockoff = pf->fc_blockoff;
+  ga.perm = pf->fc_perm;
+  launch_group(ga, s);
+}
+
+// Each class's dynamics GP on the scratch cloud X, rows in the grouped order of fc_group
+// (gpmdm_pf_predict's launches: every particle is evaluated), into fc_q / fc_mu.
+void fc_tiles(gpmdm_pf* pf, const double* X, hipStream_t s) {
+  gpmdm_model* m = pf->m;
+  const int C = m->C, d = m->d;
+  const long long P = pf->P;
+  const std::vector<GpImage>& dset = m->dyn_set(true);
+  const FcTables tb{pf->fc_tab};
+  for (int c0 = 0; c0 < C; c0 += kMaxSeg) {
+    const int ns = std::min(kMaxSeg, C - c0);
+    TileParams tp{};
+    int njm = 0;
+    for (int k = 0; k < ns; ++k) {
+      tp.seg[k] = dset[c0 + k].seg();
+      njm = std::max(njm, dset[c0 + k].n_j);
+    }
+    tp.n_seg = ns;
+    tp.geo = dset[c0].geo;
+    tp.tiles_ub = (int)(cdiv(P, tp.geo.pt()) + ns);
+    tp.n_j_max = njm;
+    tp.seg_pos_begin = tb.seg_begin() + c0;
+    tp.seg_pos_end = tb.seg_end() + c0;
+    tp.seg_out_base = tb.seg_out() + c0;
+    tp.seg_tile_start = tb.seg_tiles() + c0;
+    tp.perm = pf->fc_perm;
+    tp.X = X;
+    fill_tile_common(tp, m, true);
+    tp.qpart = pf->fc_q;
+    tp.ld_q = P;
+    tp.mu = pf->fc_mu;
+    tp.ld_mu = d;
+    launch_gp_tile(tp, d, true, s);
+  }
+}
+
 // Every launch of the roll-out.  stage_X / stage_cls (or nullptr): H x P x d / H x P device
 // rows that take each step's cloud instead of the ping-pong halves (the next step reads its
 // input there: no copy).
@@ -96,58 +150,9 @@ static int launch_rollout(gpmdm_pf* pf, int H, bool mean_only, bool obs, unsigne
         launch_fc_switch(sa, s);
         cgrp = ccur = cnext;
       }
-      ScanArgs sc{};
-      sc.nb = nb;
-      sc.C = C;
-      sc.pt = dset[0].geo.pt();
-      sc.lo = 0;
-      sc.hi = P;
-      sc.blockcounts = pf->fc_blockcounts;
-      sc.cls_new = cgrp;
-      sc.blockoff = pf->fc_blockoff;
-      sc.class_start = tb.class_start();
-      sc.counts = tb.counts();
-      sc.seg_pos_begin = tb.seg_begin();
-      sc.seg_pos_end = tb.seg_end();
-      sc.seg_out_base = tb.seg_out();
-      sc.seg_tile_start = tb.seg_tiles();
-      launch_scan_counts(sc, s);
-      GroupArgs ga{};
-      ga.P = P;
-      ga.n = P;
-      ga.C = C;
-      ga.cls_new = cgrp;
-      ga.class_start = tb.class_start();
-      ga.blockoff = pf->fc_blockoff;
-      ga.perm = pf->fc_perm;
-      launch_group(ga, s);
+      fc_group(pf, cgrp, s);
     }
-    // each class's dynamics GP on the scratch cloud, rows in grouped order (gpmdm_pf_predict)
-    for (int c0 = 0; c0 < C; c0 += kMaxSeg) {
-      const int ns = std::min(kMaxSeg, C - c0);
-      TileParams tp{};
-      int njm = 0;
-      for (int k = 0; k < ns; ++k) {
-        tp.seg[k] = dset[c0 + k].seg();
-        njm = std::max(njm, dset[c0 + k].n_j);
-      }
-      tp.n_seg = ns;
-      tp.geo = dset[c0].geo;
-      tp.tiles_ub = (int)(cdiv(P, tp.geo.pt()) + ns);
-      tp.n_j_max = njm;
-      tp.seg_pos_begin = tb.seg_begin() + c0;
-      tp.seg_pos_end = tb.seg_end() + c0;
-      tp.seg_out_base = tb.seg_out() + c0;
-      tp.seg_tile_start = tb.seg_tiles() + c0;
-      tp.perm = pf->fc_perm;
-      tp.X = Xcur;
-      fill_tile_common(tp, m, true);
-      tp.qpart = pf->fc_q;
-      tp.ld_q = P;
-      tp.mu = pf->fc_mu;
-      tp.ld_mu = d;
-      launch_gp_tile(tp, d, true, s);
-    }
+    fc_tiles(pf, Xcur, s);
     FcFinishArgs fa{};
     fa.P = P;
     fa.C = C;
@@ -208,7 +213,7 @@ extern "C" {
 int gpmdm_pf_forecast(gpmdm_pf_t pf, int horizon, int mode, const uint64_t* seed, const gpmdm_forecast_out* out,
                       void* stream) {
   CHECK(pf, "null handle");
-  CHECK(pf->F == 1, "the forecast serves single filters, not banks");
+  CHECK(pf->F == 1, "the forecast serves single filters, not banks (gpmdm_bank_forecast)");
   CHECK(horizon >= 1 && horizon <= GPMDM_FORECAST_MAX_HORIZON, "horizon must be in [1, GPMDM_FORECAST_MAX_HORIZON]");
   CHECK(mode == GPMDM_FORECAST_SAMPLE || mode == GPMDM_FORECAST_MEAN, "mode: GPMDM_FORECAST_SAMPLE or GPMDM_FORECAST_MEAN");
   if (!pf->initialised) return fail(GPMDM_E_STATE, "particle filter not initialised");

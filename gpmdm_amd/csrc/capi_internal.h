@@ -8,6 +8,7 @@
 //   capi_replay.hip    replay-draw staging (pinned buffers, staged normals, pre-switch)
 //   capi_forecast.hip  the multi-step forecast roll-out (gpmdm_pf_forecast)
 //   capi_smooth.hip    fixed-lag smoothing: the ancestry ring and its read-out (gpmdm_pf_smoothed)
+//   capi_bank_rollout.hip  both for filter banks (gpmdm_bank_forecast, gpmdm_bank_smoothed)
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -348,6 +349,9 @@ struct gpmdm_pf {
   size_t fc_out_cap = 0;
   hipEvent_t fc_ev = nullptr;
   bool fc_pending = false;
+  // (gpmdm_bank_forecast shares the scratch -- at F = 1 every size agrees -- and adds the
+  // per-block class counts of its per-filter sums, F x ceil(Pf / 256) x C)
+  int* fc_bcounts = nullptr;
   // Fixed-lag smoothing (gpmdm_pf_set_smoothing / gpmdm_pf_smoothed, smooth.h;
   // capi_smooth.hip).  sm_L > 0: every resample records {ridx, cls, X} into slot
   // frame mod (sm_L + 1) of the ring (sm_anc / sm_cls / sm_X, sm_L + 1 frames each); sm_depth =
@@ -693,7 +697,7 @@ struct gpmdm_pf {
     if (ro_obs_ev) (void)hipEventDestroy(ro_obs_ev);
     double* fd[] = {fc_X[0], fc_X[1], fc_q, fc_mu, fc_part, fc_ro_part, fc_out};
     for (double* p : fd) dfree(p);
-    int* fi[] = {fc_cls[0], fc_cls[1], fc_perm, fc_blockcounts, fc_blockoff, fc_tab};
+    int* fi[] = {fc_cls[0], fc_cls[1], fc_perm, fc_blockcounts, fc_blockoff, fc_tab, fc_bcounts};
     for (int* p : fi) dfree(p);
     hfree(fc_pin);
     if (fc_ev) (void)hipEventDestroy(fc_ev);
@@ -776,6 +780,34 @@ int quiesce_users(gpmdm_model* m);
 int sm_wait(gpmdm_pf* pf);
 int sm_record(gpmdm_pf* pf, hipStream_t s);
 int sm_clear(gpmdm_pf* pf, hipStream_t s);
+// the forecast's class tables (fc_tab): the layout of gpmdm_pf::small's (class_start, counts, segments)
+struct FcTables {
+  int* t;
+  int* class_start() const { return t; }
+  int* counts() const { return t + 40; }
+  int* seg_begin() const { return t + 80; }
+  int* seg_end() const { return t + 120; }
+  int* seg_out() const { return t + 160; }
+  int* seg_tiles() const { return t + 200; }
+};
+// the roll-out's grouping and dynamics-tile launches (capi_forecast.hip), shared with the banks'
+void fc_group(gpmdm_pf* pf, const int* cls, hipStream_t s);
+void fc_tiles(gpmdm_pf* pf, const double* X, hipStream_t s);
+int sm_set(gpmdm_pf* pf, int lag);     // (set_smoothing of a checked handle, single or bank)
+// staging of a forecast's per-step clouds may take this much device memory (H x P x (d + 1)
+// doubles); so may the smoothing ring, and a smoothed read-out's staging of the particle rows
+constexpr size_t kForecastStageBytes = (size_t)1 << 30;
+constexpr size_t kSmoothBytes = (size_t)1 << 30;
+// a read-out's scratch grown inside a call: the old buffer is released after s's earlier work
+template <typename T>
+int grow(T*& p, size_t& cap, size_t n, hipStream_t s) {
+  if (cap >= n) return GPMDM_OK;
+  dfree_after(p, s);
+  cap = 0;
+  TRY(dalloc(&p, n));
+  cap = n;
+  return GPMDM_OK;
+}
 int h2d(void* dst, const void* src, size_t bytes);
 // the observation-GP cutoff image (capi_model.hip; packed on the host or the device)
 struct CutoffPlan {

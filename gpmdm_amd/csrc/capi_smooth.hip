@@ -8,9 +8,6 @@
 
 namespace gpmdm::capi {
 
-// the ring, and a read-out's staging of the particle rows, may take this much device memory
-constexpr size_t kSmoothBytes = (size_t)1 << 30;
-
 static size_t ring_bytes(long long P, int d, int L) {
   return (size_t)(L + 1) * (size_t)P * (sizeof(double) * d + 2 * sizeof(int));
 }
@@ -65,23 +62,8 @@ int sm_clear(gpmdm_pf* pf, hipStream_t s) {
   return GPMDM_OK;
 }
 
-template <typename T>
-static int grow(T*& p, size_t& cap, size_t n, hipStream_t s) {
-  if (cap >= n) return GPMDM_OK;
-  dfree_after(p, s);                   // (after the stream's earlier work)
-  cap = 0;
-  TRY(dalloc(&p, n));
-  cap = n;
-  return GPMDM_OK;
-}
-
-}  // namespace gpmdm::capi
-
-extern "C" {
-
-int gpmdm_pf_set_smoothing(gpmdm_pf_t pf, int lag) {
-  CHECK(pf, "null handle");
-  CHECK(pf->F == 1, "smoothing serves single filters, not banks");
+// gpmdm_pf_set_smoothing / gpmdm_bank_set_smoothing on a checked handle (P: all F x Pf particles)
+int sm_set(gpmdm_pf* pf, int lag) {
   CHECK(lag >= 0 && lag <= GPMDM_SMOOTH_MAX_LAG, "lag must be in [0, GPMDM_SMOOTH_MAX_LAG]");
   if ((pf->switched && !pf->preswitched) || pf->dyn_done || pf->propagated)
     return fail(GPMDM_E_STATE, "set_smoothing between switch and resample");
@@ -113,6 +95,16 @@ int gpmdm_pf_set_smoothing(gpmdm_pf_t pf, int lag) {
   return sm_clear(pf, ls);
 }
 
+}  // namespace gpmdm::capi
+
+extern "C" {
+
+int gpmdm_pf_set_smoothing(gpmdm_pf_t pf, int lag) {
+  CHECK(pf, "null handle");
+  CHECK(pf->F == 1, "smoothing serves single filters, not banks (gpmdm_bank_set_smoothing)");
+  return sm_set(pf, lag);
+}
+
 int gpmdm_pf_smoothing_depth(gpmdm_pf_t pf, int* lag, int* depth) {
   CHECK(pf, "null handle");
   if (lag) *lag = pf->sm_L;
@@ -122,7 +114,7 @@ int gpmdm_pf_smoothing_depth(gpmdm_pf_t pf, int* lag, int* depth) {
 
 int gpmdm_pf_smoothed(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_smoothed_out* out, void* stream) {
   CHECK(pf, "null handle");
-  CHECK(pf->F == 1, "smoothing serves single filters, not banks");
+  CHECK(pf->F == 1, "smoothing serves single filters, not banks (gpmdm_bank_smoothed)");
   CHECK(pf->sm_L > 0, "smoothing is off (gpmdm_pf_set_smoothing)");
   if (!pf->initialised) return fail(GPMDM_E_STATE, "particle filter not initialised");
   // (a pending pre-switch reads the cloud and writes the step's tables: neither is the smoother's)

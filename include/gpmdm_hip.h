@@ -521,7 +521,7 @@ int gpmdm_bank_observation(gpmdm_pf_t pf, double* mean, double* spread, void* st
  * doubles for the call's duration: GPMDM_E_INVALID above 1 GiB.  horizon in
  * [1, GPMDM_FORECAST_MAX_HORIZON].  Between a switch and its resample: GPMDM_E_STATE.  A
  * sharded filter forecasts its replicated cloud on the handle it is called on.  Banks:
- * GPMDM_E_INVALID. */
+ * GPMDM_E_INVALID (gpmdm_bank_forecast). */
 enum { GPMDM_FORECAST_SAMPLE = 0, GPMDM_FORECAST_MEAN = 1 };
 #define GPMDM_FORECAST_MAX_HORIZON 4096
 typedef struct gpmdm_forecast_out {   /* host arrays; any may be NULL */
@@ -570,7 +570,8 @@ int gpmdm_pf_forecast(gpmdm_pf_t pf, int horizon, int mode, const uint64_t* seed
  * clouds a pose reads) are staged on the device for the call's duration: GPMDM_E_INVALID above
  * 1 GiB.  Between a switch and its resample: GPMDM_E_STATE.  Every rank of a sharded filter
  * records its replicated cloud; the read-out serves the handle it is called on.  Banks:
- * GPMDM_E_INVALID. */
+ * GPMDM_E_INVALID (gpmdm_bank_set_smoothing, gpmdm_bank_smoothed; gpmdm_pf_smoothing_depth
+ * serves any handle). */
 #define GPMDM_SMOOTH_MAX_LAG 4096
 typedef struct gpmdm_smoothed_out {   /* host arrays; any may be NULL; n = lag_last - lag_first + 1 */
   double*  class_prob;   /* n x C */
@@ -586,6 +587,42 @@ int gpmdm_pf_set_smoothing(gpmdm_pf_t pf, int lag);
 int gpmdm_pf_smoothing_depth(gpmdm_pf_t pf, int* lag, int* depth);
 int gpmdm_pf_smoothed(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_smoothed_out* out,
                       void* stream);
+
+/* Forecasts and fixed-lag smoothing for filter banks: gpmdm_pf_forecast, gpmdm_pf_set_smoothing
+ * and gpmdm_pf_smoothed for every filter of a bank in one sequence of launches.  Any handle
+ * (F = 1 included).  The same limits and the same call-order rule hold (GPMDM_FORECAST_MAX_HORIZON,
+ * GPMDM_SMOOTH_MAX_LAG, GPMDM_E_STATE between a switch and its resample), and the 1 GiB caps of
+ * the forecast's staging, the history and the smoothed read-out's staging count all F x P
+ * particles.  The outputs are gpmdm_forecast_out / gpmdm_smoothed_out with one more axis,
+ * step-major (lag-major), then filter-major -- the order the device holds them in:
+ *   class_prob [H][F][C]   state_mean [H][F][d]   obs_mean / obs_spread [H][F][D]
+ *   states [H][F][P][d]    classes / ancestors [H][F][P]    distinct [n][F]
+ * with P the particles per filter; ancestors are in-filter indices in [0, P).
+ * Row f is the single filter's result on filter f's cloud.  Forecast: filter f draws with the
+ * key *seed + f (NULL: the handle's seed, so the filter's own key) and its in-filter particle
+ * index in the counter, so class_prob, obs_mean, obs_spread, states and classes are bitwise
+ * gpmdm_pf_forecast's with seed *seed + f on a filter holding f's cloud at the same frame.
+ * state_mean differs from that call in summation order only: a bank sums each filter's new
+ * cloud in particle order, in blocks of 256 cut within the filter (wave butterfly, the four
+ * waves in order, then the blocks' sums as gpmdm_pf_smoothed reduces them), because the single
+ * call's grouped-order blocks would mix filters; the value depends on the filter's own cloud
+ * alone -- not on the horizon, the other filters or how a bank is split into handles.  The
+ * grouping and the dynamics tiles run once over all F x P particles, the class counts are
+ * integers per (filter, class), and each step's pose is one read-out launch over the F clouds.
+ * Smoothing: gpmdm_bank_set_smoothing keeps (lag + 1) x F x P rows; every resample of the bank
+ * (each of its resampling paths, the cutoff's included) records behind its read-out, and
+ * gpmdm_pf_init, gpmdm_pf_import, gpmdm_pf_set_model and gpmdm_bank_set_smoothing clear the
+ * history as for a single filter.  The trace walks each filter's rows only, in blocks of 256 cut
+ * within the filter -- the single filter's blocks -- so every field, state_mean included, is
+ * bitwise gpmdm_pf_smoothed's on a single filter with the same history.  A bank with smoothing
+ * off issues exactly the work it issued before.  Both calls queue everything on `stream`, end
+ * with one pinned copy and one wait, release their staging in stream order, and are covered by
+ * the handle's lifecycle waits. */
+int gpmdm_bank_forecast(gpmdm_pf_t pf, int horizon, int mode, const uint64_t* seed,
+                        const gpmdm_forecast_out* out, void* stream);
+int gpmdm_bank_set_smoothing(gpmdm_pf_t pf, int lag);
+int gpmdm_bank_smoothed(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_smoothed_out* out,
+                        void* stream);
 
 /* Device-side GP factor: the recipe of _precompute_kernel_inverses
  * (gpmdm.py:1284-1305) for one GP block -- the observation GP, or one class block of the
