@@ -28,7 +28,7 @@ import torch
 from . import _lib, replay
 from .distributed import shard_range
 from .model import GPMDM
-from .pf import Forecast, Smoothed, _check_lag_range, _check_smoothing_lag
+from .pf import Forecast, Smoothed, _check_smoothing_lag, _forecast_call, _smoothed_call
 
 
 def _filter_major(a):
@@ -313,29 +313,10 @@ class GPMDM_PF_Bank:
         (the single filter sums in class-grouped order): the same mean to rounding, bitwise
         reproducible, independent of ``horizon`` and identical between a full bank and the
         shards of a sharded one.  The bank is not changed by the call."""
-        if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)):
-            raise ValueError(f"horizon must be an integer, got {horizon!r}")
-        H = int(horizon)
-        if not 1 <= H <= _lib.GPMDM_FORECAST_MAX_HORIZON:
-            raise ValueError(f"horizon must be in [1, {_lib.GPMDM_FORECAST_MAX_HORIZON}], got {H}")
-        if mode not in _lib.FORECAST_MODES:
-            raise ValueError(f"mode must be one of {sorted(_lib.FORECAST_MODES)}, got {mode!r}")
-        Fl, P, C, d, D = self.local_filters, self._num_particles, self.num_classes, self.latent_dim, self.observation_dim
-        # the library's layout: step-major, then filter-major
-        cp, sm = np.zeros((H, Fl, C)), np.zeros((H, Fl, d))
-        om = np.zeros((H, Fl, D)) if observation else None
-        osp = np.zeros((H, Fl, D)) if observation else None
-        st = np.zeros((H, Fl, P, d)) if particles else None
-        cl = np.zeros((H, Fl, P), dtype=np.int64) if particles else None
-        if self._h is not None:
-            self._sync_model()
-            out = _lib.ForecastOut(_lib.dptr(cp), _lib.dptr(sm), _lib.dptr(om), _lib.dptr(osp), _lib.dptr(st),
-                                   _lib.i64ptr(cl))
-            # (the handle's filter 0 is the bank's filter f_lo)
-            sd = None if seed is None else ctypes.byref(ctypes.c_uint64((int(seed) + self._f_lo) & (2 ** 64 - 1)))
-            _lib.check(_lib.load().gpmdm_bank_forecast(self._h, H, _lib.FORECAST_MODES[mode], sd, ctypes.byref(out),
-                                                       self._stream()), "forecast")
-        return Forecast(*(_filter_major(a) for a in (cp, sm, om, osp, st, cl)))
+        # (the handle's filter 0 is the bank's filter f_lo)
+        arrays = _forecast_call(self, None if self._h is None else "gpmdm_bank_forecast", (self.local_filters,),
+                                horizon, mode, observation, particles, None if seed is None else int(seed) + self._f_lo)
+        return Forecast(*map(_filter_major, arrays))
 
     def set_smoothing(self, lag: int):
         """``GPMDM_PF.set_smoothing`` for the bank (gpmdm_bank_set_smoothing): keep the last
@@ -376,30 +357,9 @@ class GPMDM_PF_Bank:
         ``ancestors`` (in-filter indices) and ``classes`` (F_local, n, P) and ``states``
         (F_local, n, P, d).  Row f is bitwise ``GPMDM_PF.smoothed`` of a single filter with the
         same history, ``state_mean`` included.  The bank is not changed by the call."""
-        first, last = _check_lag_range(lag)
-        if not self._smoothing_lag:
-            raise ValueError("smoothing is off: build the bank with smoothing_lag=L or call set_smoothing(L)")
-        depth = self.smoothing_depth
-        if last is None:
-            last = depth
-        if last > depth:
-            raise ValueError(f"lag {last} is above the recorded depth {depth} (smoothing lag {self._smoothing_lag})")
-        Fl, P, C, d, D = self.local_filters, self._num_particles, self.num_classes, self.latent_dim, self.observation_dim
-        n = last - first + 1
-        cp, sm, da = np.zeros((n, Fl, C)), np.zeros((n, Fl, d)), np.zeros((n, Fl), dtype=np.int64)
-        om = np.zeros((n, Fl, D)) if observation else None
-        osp = np.zeros((n, Fl, D)) if observation else None
-        an = np.zeros((n, Fl, P), dtype=np.int64) if particles else None
-        st = np.zeros((n, Fl, P, d)) if particles else None
-        cl = np.zeros((n, Fl, P), dtype=np.int64) if particles else None
-        if self._h is not None:
-            out = _lib.SmoothedOut(_lib.dptr(cp), _lib.dptr(sm), _lib.i64ptr(da), _lib.dptr(om), _lib.dptr(osp),
-                                   _lib.i64ptr(an), _lib.dptr(st), _lib.i64ptr(cl))
-            _lib.check(_lib.load().gpmdm_bank_smoothed(self._h, first, last, ctypes.byref(out), self._stream()),
-                       "smoothed")
-        lags = np.arange(first, last + 1, dtype=np.int64)
-        return Smoothed(torch.from_numpy(lags), torch.from_numpy(self.frame - lags),
-                        *(_filter_major(a) for a in (cp, sm, da, om, osp, an, st, cl)))
+        lags, rest = _smoothed_call(self, "bank", None if self._h is None else "gpmdm_bank_smoothed",
+                                    (self.local_filters,), lag, observation, particles)
+        return Smoothed(torch.from_numpy(lags), torch.from_numpy(self.frame - lags), *map(_filter_major, rest))
 
     def health(self, reset: bool = False) -> dict:
         """Failure counters of the local filters together since creation (or the last reset):

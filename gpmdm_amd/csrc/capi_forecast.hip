@@ -1,18 +1,24 @@
-// C ABI, the forecast roll-out (gpmdm_pf_forecast): H steps of the filter's proposal on a
-// scratch copy of the cloud, all queued on the caller's stream -- per step the roll-out switch,
-// the filter's grouping passes on the forecast's own tables, the dynamics-GP tiles as predict()
-// launches them, the roll-out finish and reduce, and the pose read-out pointed at the scratch
-// cloud -- then one copy-back and one wait.  Kernels: forecast.h.
+// C ABI, the forecast roll-out (gpmdm_pf_forecast, gpmdm_bank_forecast): H steps of the filter's
+// proposal on a scratch copy of the cloud, all queued on the caller's stream -- per step the
+// roll-out switch, the filter's grouping passes on the forecast's own tables, the dynamics-GP
+// tiles as predict() launches them, the roll-out finish, (the bank entry's) per-filter sum and
+// the reduce, and the pose read-out pointed at the scratch cloud -- then one copy-back and one
+// wait.  Grouping and tiles run over all F x Pf particles; sums, counts and the pose per filter.
+// The two entry points differ in their handle checks and in who sums the mean state
+// (forecast.h); every device result is step-major, then filter-major.  Kernels: forecast.h.
 #include "capi_internal.h"
 #include "forecast.h"
 
 namespace gpmdm::capi {
 
-static int ensure_scratch(gpmdm_pf* pf, int H, bool obs) {
+// Scratch of both entry points, and H x F result rows: {class_prob[C], state_mean[d]} of every
+// (step, filter), then {mean[D], spread[D]} of every (step, filter) -- the read-out writes the
+// F filters of a step as one contiguous block.
+static int ensure_scratch(gpmdm_pf* pf, int H, bool obs, bool per_filter_sums) {
   const gpmdm_model* m = pf->m;
-  const int C = m->C, d = m->d, D = m->D;
+  const int C = m->C, d = m->d, D = m->D, F = pf->F;
   const long long P = pf->P;
-  const long long nb = cdiv(P, 256);
+  const long long nb = cdiv(P, 256), nbf = cdiv(pf->Pf, 256);
 #define NEED(ptr, n) do { if (!(ptr)) TRY(dalloc(&(ptr), (size_t)(n))); } while (0)
   for (int k = 0; k < 2; ++k) {
     NEED(pf->fc_X[k], P * d);
@@ -22,7 +28,8 @@ static int ensure_scratch(gpmdm_pf* pf, int H, bool obs) {
   NEED(pf->fc_blockcounts, nb * C);
   NEED(pf->fc_blockoff, nb * C);
   NEED(pf->fc_mu, P * d);
-  NEED(pf->fc_part, nb * d);
+  NEED(pf->fc_part, F * nbf * d);
+  if (per_filter_sums) NEED(pf->fc_bcounts, F * nbf * C);
   NEED(pf->fc_tab, 256);
 #undef NEED
   const size_t qn = (size_t)pf->nparts_dyn_max * P;
@@ -32,8 +39,8 @@ static int ensure_scratch(gpmdm_pf* pf, int H, bool obs) {
     TRY(dalloc(&pf->fc_q, qn));
     pf->fc_q_cap = qn;
   }
-  if (obs && !pf->fc_ro_part) TRY(dalloc(&pf->fc_ro_part, readout_part_doubles(P, D)));
-  const size_t on = (size_t)H * (C + d + 2 * D);
+  if (obs && !pf->fc_ro_part) TRY(dalloc(&pf->fc_ro_part, readout_part_doubles(pf->Pf, D, F)));
+  const size_t on = (size_t)H * F * (C + d + 2 * D);
   if (pf->fc_out_cap < on) {
     dfree(pf->fc_out);
     hfree(pf->fc_pin);
@@ -46,9 +53,27 @@ static int ensure_scratch(gpmdm_pf* pf, int H, bool obs) {
   return GPMDM_OK;
 }
 
+ReadoutParams rollout_readout(const gpmdm_pf* pf, const double* X, double* part, double* out) {
+  const gpmdm_model* m = pf->m;
+  ReadoutParams rp{};
+  rp.X = X;
+  rp.P = pf->Pf;
+  rp.F = pf->F;
+  rp.d = m->d;
+  rp.D = m->D;
+  rp.ls = m->y_ls_dev;
+  rp.Xrec = m->obs.Xrec;
+  rp.nks = ksteps((int)m->N);
+  rp.Bro = m->ro_beta;
+  rp.n_groups = readout_groups(m->D);
+  rp.part = part;
+  rp.out = out;
+  return rp;
+}
+
 // The filter's grouping passes on the forecast's own tables: classes `cls` (all pf->P particles,
 // a bank's F x Pf among them), whose per-block counts are in fc_blockcounts.
-void fc_group(gpmdm_pf* pf, const int* cls, hipStream_t s) {
+static void fc_group(gpmdm_pf* pf, const int* cls, hipStream_t s) {
   const gpmdm_model* m = pf->m;
   const long long P = pf->P;
   const FcTables tb{pf->fc_tab};
@@ -81,7 +106,7 @@ void fc_group(gpmdm_pf* pf, const int* cls, hipStream_t s) {
 
 // Each class's dynamics GP on the scratch cloud X, rows in the grouped order of fc_group
 // (gpmdm_pf_predict's launches: every particle is evaluated), into fc_q / fc_mu.
-void fc_tiles(gpmdm_pf* pf, const double* X, hipStream_t s) {
+static void fc_tiles(gpmdm_pf* pf, const double* X, hipStream_t s) {
   gpmdm_model* m = pf->m;
   const int C = m->C, d = m->d;
   const long long P = pf->P;
@@ -114,30 +139,33 @@ void fc_tiles(gpmdm_pf* pf, const double* X, hipStream_t s) {
   }
 }
 
-// Every launch of the roll-out.  stage_X / stage_cls (or nullptr): H x P x d / H x P device
-// rows that take each step's cloud instead of the ping-pong halves (the next step reads its
-// input there: no copy).
-static int launch_rollout(gpmdm_pf* pf, int H, bool mean_only, bool obs, unsigned seed_lo, unsigned seed_hi,
-                          double* stage_X, int* stage_cls, hipStream_t s) {
+// Every launch of the roll-out.  per_filter_sums: k_fc_sum sums the new cloud and counts its
+// classes per filter (gpmdm_bank_forecast, whatever F); else the finish sums its own blocks and
+// the class counts are the grouping's (gpmdm_pf_forecast, F = 1).  stage_X / stage_cls (or
+// nullptr): H x P x d / H x P device rows that take each step's cloud instead of the ping-pong
+// halves (the next step reads its input there: no copy).
+static int launch_rollout(gpmdm_pf* pf, int H, bool mean_only, bool obs, bool per_filter_sums, unsigned seed_lo,
+                          unsigned seed_hi, double* stage_X, int* stage_cls, hipStream_t s) {
   gpmdm_model* m = pf->m;
-  const int C = m->C, d = m->d, D = m->D;
-  const long long P = pf->P;
-  const int nb = (int)cdiv(P, 256);
-  const int W = C + d + 2 * D;
+  const int C = m->C, d = m->d, D = m->D, F = pf->F;
+  const long long P = pf->P, Pf = pf->Pf;
+  const int nbf = (int)cdiv(Pf, 256);
   const std::vector<GpImage>& dset = m->dyn_set(true);   // every particle is evaluated: predict()'s images
   const FcTables tb{pf->fc_tab};
+  double* out_ro = pf->fc_out + (size_t)H * F * (C + d);
   const double* Xcur = pf->X;
   const int* ccur = pf->cls;
   for (int h = 0; h < H; ++h) {
     double* Xnext = stage_X ? stage_X + (size_t)h * P * d : pf->fc_X[h & 1];
-    if (!mean_only || h == 0) {         // (mean mode: classes frozen, one grouping serves every step)
-      const int* cgrp = ccur;
+    const bool regroup = !mean_only || h == 0;   // (mean mode: classes frozen, one grouping and one count)
+    if (regroup) {
       if (mean_only) {
         launch_class_hist(ccur, P, C, pf->fc_blockcounts, s);
       } else {
         int* cnext = stage_cls ? stage_cls + (size_t)h * P : pf->fc_cls[h & 1];
         FcSwitchArgs sa{};
         sa.P = P;
+        sa.Pf = Pf;
         sa.C = C;
         sa.h = (unsigned)(h + 1);
         sa.frame = pf->frame;
@@ -148,13 +176,14 @@ static int launch_rollout(gpmdm_pf* pf, int H, bool mean_only, bool obs, unsigne
         sa.T = pf->T;
         sa.blockcounts = pf->fc_blockcounts;
         launch_fc_switch(sa, s);
-        cgrp = ccur = cnext;
+        ccur = cnext;
       }
-      fc_group(pf, cgrp, s);
+      fc_group(pf, ccur, s);
     }
     fc_tiles(pf, Xcur, s);
     FcFinishArgs fa{};
     fa.P = P;
+    fa.Pf = Pf;
     fa.C = C;
     fa.d = d;
     fa.mean_only = mean_only ? 1 : 0;
@@ -173,68 +202,59 @@ static int launch_rollout(gpmdm_pf* pf, int H, bool mean_only, bool obs, unsigne
     for (int j = 0; j <= d; ++j) fa.lin_c2[j] = m->x_lin_c2[j];
     for (int j = 0; j < d; ++j) fa.il2[j] = m->x_il2[j];
     fa.X_out = Xnext;
-    fa.partials = pf->fc_part;
+    fa.partials = per_filter_sums ? nullptr : pf->fc_part;
     launch_fc_finish(fa, s);
+    if (per_filter_sums) {               // the new cloud's sums in particle order, and the step's class counts
+      FcSumArgs ua{};
+      ua.Pf = Pf;
+      ua.C = C;
+      ua.d = d;
+      ua.X = Xnext;
+      ua.cls = regroup ? ccur : nullptr;
+      ua.bcounts = pf->fc_bcounts;
+      ua.partials = pf->fc_part;
+      launch_fc_sum(ua, F, s);
+    }
     FcReduceArgs ra{};
-    ra.P = P;
+    ra.Pf = Pf;
     ra.C = C;
     ra.d = d;
-    ra.nb = nb;
-    ra.counts = tb.counts();
+    ra.nbf = nbf;
+    ra.n_count_rows = per_filter_sums ? nbf : 1;
+    ra.counts = per_filter_sums ? pf->fc_bcounts : tb.counts();
     ra.partials = pf->fc_part;
-    ra.out = pf->fc_out + (size_t)h * W;
-    launch_fc_reduce(ra, s);
-    if (obs) {
-      ReadoutParams rp{};
-      rp.X = Xnext;
-      rp.P = P;
-      rp.F = 1;
-      rp.d = d;
-      rp.D = D;
-      rp.ls = m->y_ls_dev;
-      rp.Xrec = m->obs.Xrec;
-      rp.nks = ksteps((int)m->N);
-      rp.Bro = m->ro_beta;
-      rp.n_groups = readout_groups(D);
-      rp.part = pf->fc_ro_part;
-      rp.out = pf->fc_out + (size_t)h * W + C + d;   // {mean[D], spread[D]} of row h
-      launch_obs_readout(rp, s);
-    }
+    ra.out = pf->fc_out + (size_t)h * F * (C + d);
+    launch_fc_reduce(ra, F, s);
+    if (obs)                             // the step's pose: one read-out over the F clouds
+      launch_obs_readout(rollout_readout(pf, Xnext, pf->fc_ro_part, out_ro + (size_t)h * F * 2 * D), s);
     Xcur = Xnext;
     HIPCHK(hipGetLastError());
   }
   return GPMDM_OK;
 }
 
-}  // namespace gpmdm::capi
-
-extern "C" {
-
-int gpmdm_pf_forecast(gpmdm_pf_t pf, int horizon, int mode, const uint64_t* seed, const gpmdm_forecast_out* out,
-                      void* stream) {
-  CHECK(pf, "null handle");
-  CHECK(pf->F == 1, "the forecast serves single filters, not banks (gpmdm_bank_forecast)");
+// The body of both entry points on a checked handle.  stage_refusal: the entry point's wording
+// of the 1 GiB staging limit.
+static int forecast(gpmdm_pf* pf, int horizon, int mode, const uint64_t* seed, const gpmdm_forecast_out* out,
+                    void* stream, bool per_filter_sums, const char* stage_refusal) {
   CHECK(horizon >= 1 && horizon <= GPMDM_FORECAST_MAX_HORIZON, "horizon must be in [1, GPMDM_FORECAST_MAX_HORIZON]");
   CHECK(mode == GPMDM_FORECAST_SAMPLE || mode == GPMDM_FORECAST_MEAN, "mode: GPMDM_FORECAST_SAMPLE or GPMDM_FORECAST_MEAN");
   if (!pf->initialised) return fail(GPMDM_E_STATE, "particle filter not initialised");
   // (a pending pre-switch reads the cloud and writes the step's tables: neither is the forecast's)
-  if ((pf->switched && !pf->preswitched) || pf->dyn_done || pf->propagated)
-    return fail(GPMDM_E_STATE, "forecast between switch and resample");
+  if (pf->mid_step()) return fail(GPMDM_E_STATE, "forecast between switch and resample");
   gpmdm_model* m = pf->m;
   HIPCHK(hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
-  const int C = m->C, d = m->d, D = m->D, H = horizon;
+  const int C = m->C, d = m->d, D = m->D, H = horizon, F = pf->F;
   const long long P = pf->P;
-  const int W = C + d + 2 * D;
   const bool mean_only = mode == GPMDM_FORECAST_MEAN;
   static const gpmdm_forecast_out none{};
   const gpmdm_forecast_out& o = out ? *out : none;
   const bool obs = o.obs_mean || o.obs_spread;
   if (o.states || o.classes)
-    CHECK((size_t)H * (size_t)P * (size_t)(d + 1) <= kForecastStageBytes / sizeof(double),
-          "states / classes of this forecast need more than 1 GiB of device staging (H x P x (d + 1) doubles)");
+    CHECK((size_t)H * (size_t)P * (size_t)(d + 1) <= kForecastStageBytes / sizeof(double), stage_refusal);
   const unsigned long long sd = seed ? *seed : (((unsigned long long)pf->seed_hi << 32) | pf->seed_lo);
-  TRY(ensure_scratch(pf, H, obs));
+  TRY(ensure_scratch(pf, H, obs, per_filter_sums));
   // per-call staging of the clouds, released in the stream's order on every exit
   double* stage_X = nullptr;
   int* stage_cls = nullptr;
@@ -243,14 +263,16 @@ int gpmdm_pf_forecast(gpmdm_pf_t pf, int horizon, int mode, const uint64_t* seed
     dfree(stage_X);
     return GPMDM_E_NOMEM;
   }
-  int rc = launch_rollout(pf, H, mean_only, obs, (unsigned)(sd & 0xffffffffu), (unsigned)(sd >> 32), stage_X,
-                          stage_cls, s);
+  int rc = launch_rollout(pf, H, mean_only, obs, per_filter_sums, (unsigned)(sd & 0xffffffffu), (unsigned)(sd >> 32),
+                          stage_X, stage_cls, s);
+  const size_t n_rows = (size_t)H * F;
+  const size_t n_out = n_rows * (C + d) + (obs ? n_rows * 2 * D : 0);
   std::vector<int> c32;
   auto copies = [&]() -> int {
-    HIPCHK(hipMemcpyAsync(pf->fc_pin, pf->fc_out, sizeof(double) * H * W, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pf->fc_pin, pf->fc_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
     if (o.states) HIPCHK(hipMemcpyAsync(o.states, stage_X, sizeof(double) * H * P * d, hipMemcpyDeviceToHost, s));
     if (o.classes) {
-      c32.resize((size_t)(mean_only ? 1 : H) * P);   // (mean mode: the filter's classes, every step)
+      c32.resize((size_t)(mean_only ? 1 : H) * P);   // (mean mode: the filters' classes, every step)
       HIPCHK(hipMemcpyAsync(c32.data(), mean_only ? pf->cls : stage_cls, sizeof(int) * c32.size(),
                             hipMemcpyDeviceToHost, s));
     }
@@ -264,16 +286,38 @@ int gpmdm_pf_forecast(gpmdm_pf_t pf, int horizon, int mode, const uint64_t* seed
   if (rc != GPMDM_OK) return rc;
   HIPCHK(hipStreamSynchronize(s));
   pf->fc_pending = false;
-  for (int h = 0; h < H; ++h) {
-    const double* row = pf->fc_pin + (size_t)h * W;
-    if (o.class_prob) std::memcpy(o.class_prob + (size_t)h * C, row, sizeof(double) * C);
-    if (o.state_mean) std::memcpy(o.state_mean + (size_t)h * d, row + C, sizeof(double) * d);
-    if (o.obs_mean) std::memcpy(o.obs_mean + (size_t)h * D, row + C + d, sizeof(double) * D);
-    if (o.obs_spread) std::memcpy(o.obs_spread + (size_t)h * D, row + C + d + D, sizeof(double) * D);
+  const double* ro = pf->fc_pin + n_rows * (C + d);
+  for (size_t q = 0; q < n_rows; ++q) {  // q = h * F + f
+    const double* row = pf->fc_pin + q * (C + d);
+    if (o.class_prob) std::memcpy(o.class_prob + q * C, row, sizeof(double) * C);
+    if (o.state_mean) std::memcpy(o.state_mean + q * d, row + C, sizeof(double) * d);
+    if (o.obs_mean) std::memcpy(o.obs_mean + q * D, ro + q * 2 * D, sizeof(double) * D);
+    if (o.obs_spread) std::memcpy(o.obs_spread + q * D, ro + q * 2 * D + D, sizeof(double) * D);
   }
   if (o.classes)
     for (size_t i = 0; i < (size_t)H * P; ++i) o.classes[i] = c32[mean_only ? i % (size_t)P : i];
   return GPMDM_OK;
+}
+
+}  // namespace gpmdm::capi
+
+extern "C" {
+
+int gpmdm_pf_forecast(gpmdm_pf_t pf, int horizon, int mode, const uint64_t* seed, const gpmdm_forecast_out* out,
+                      void* stream) {
+  CHECK(pf, "null handle");
+  CHECK(pf->F == 1, "the forecast serves single filters, not banks (gpmdm_bank_forecast)");
+  return forecast(pf, horizon, mode, seed, out, stream, false,
+                  "states / classes of this forecast need more than 1 GiB of device staging (H x P x (d + 1) doubles)");
+}
+
+int gpmdm_bank_forecast(gpmdm_pf_t pf, int horizon, int mode, const uint64_t* seed, const gpmdm_forecast_out* out,
+                        void* stream) {
+  CHECK(pf, "null handle");
+  CHECK(pf->F <= 65535, "the bank forecast serves up to 65535 filters");
+  return forecast(pf, horizon, mode, seed, out, stream, true,
+                  "states / classes of this forecast need more than 1 GiB of device staging (H x F x P x (d + 1) "
+                  "doubles)");
 }
 
 }  // extern "C"

@@ -6,9 +6,9 @@
 //   capi_frame.hip     the per-frame launch sequence: switch, propagate, weigh, resample, read
 //   capi_exchange.hip  the multi-rank exchange (pack / unpack, RCCL communicator, gathers)
 //   capi_replay.hip    replay-draw staging (pinned buffers, staged normals, pre-switch)
-//   capi_forecast.hip  the multi-step forecast roll-out (gpmdm_pf_forecast)
-//   capi_smooth.hip    fixed-lag smoothing: the ancestry ring and its read-out (gpmdm_pf_smoothed)
-//   capi_bank_rollout.hip  both for filter banks (gpmdm_bank_forecast, gpmdm_bank_smoothed)
+//   capi_forecast.hip  the multi-step forecast roll-out (gpmdm_pf_forecast, gpmdm_bank_forecast)
+//   capi_smooth.hip    fixed-lag smoothing: the ancestry ring and its read-out (gpmdm_pf_smoothed,
+//                      gpmdm_bank_smoothed)
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -332,34 +332,33 @@ struct gpmdm_pf {
   double *ro_part = nullptr, *ro_obs = nullptr, *ro_obs_pin = nullptr;
   hipEvent_t ro_obs_ev = nullptr;
   bool ro_obs_pending = false;
-  // The forecast roll-out (gpmdm_pf_forecast, forecast.h; capi_forecast.hip): scratch of its
-  // own, allocated on first use -- the two halves of the ping-pong cloud, the grouping's
-  // tables (the layout of `small`'s, base 0), block counts / offsets and permutation, the
-  // dynamics tiles' outputs, the finish's block sums, the pose read-out's partials, and the
-  // H x (C + d + 2 D) result rows with their pinned landing buffer (grown on demand).  None
+  // The forecast roll-out (gpmdm_pf_forecast / gpmdm_bank_forecast, forecast.h;
+  // capi_forecast.hip): scratch of its own, allocated on first use -- the two halves of the
+  // ping-pong cloud, the grouping's tables (the layout of `small`'s, base 0), block counts /
+  // offsets and permutation, the dynamics tiles' outputs, the per-filter blocks' state sums
+  // (F x ceil(Pf / 256) x d) and class counts (x C: gpmdm_bank_forecast's, on its first call),
+  // the pose read-out's partials, and the H x F x (C + d + 2 D) result rows with their pinned
+  // landing buffer (grown on demand).  None
   // of it is shared with the step, the pre-switch, predict() or the read-out, so a forecast
   // leaves a pending pre-switch pending.  fc_ev follows a forecast's launches (quiesce waits
   // for it while fc_pending: the call itself synchronises, so only after a failed one).
   double* fc_X[2] = {nullptr, nullptr};
   int* fc_cls[2] = {nullptr, nullptr};
-  int *fc_perm = nullptr, *fc_blockcounts = nullptr, *fc_blockoff = nullptr, *fc_tab = nullptr;
+  int *fc_perm = nullptr, *fc_blockcounts = nullptr, *fc_blockoff = nullptr, *fc_tab = nullptr, *fc_bcounts = nullptr;
   double *fc_q = nullptr, *fc_mu = nullptr, *fc_part = nullptr, *fc_ro_part = nullptr;
   size_t fc_q_cap = 0;
   double *fc_out = nullptr, *fc_pin = nullptr;
   size_t fc_out_cap = 0;
   hipEvent_t fc_ev = nullptr;
   bool fc_pending = false;
-  // (gpmdm_bank_forecast shares the scratch -- at F = 1 every size agrees -- and adds the
-  // per-block class counts of its per-filter sums, F x ceil(Pf / 256) x C)
-  int* fc_bcounts = nullptr;
-  // Fixed-lag smoothing (gpmdm_pf_set_smoothing / gpmdm_pf_smoothed, smooth.h;
+  // Fixed-lag smoothing (gpmdm_pf_set_smoothing / gpmdm_pf_smoothed and the banks', smooth.h;
   // capi_smooth.hip).  sm_L > 0: every resample records {ridx, cls, X} into slot
   // frame mod (sm_L + 1) of the ring (sm_anc / sm_cls / sm_X, sm_L + 1 frames each); sm_depth =
   // min(sm_L, frames recorded since the ring was last cleared), the root of a cleared ring
   // being the cloud the filter held then (sm_clear records it).  The record launch follows the
   // frame's read-out number, which quiesce takes for the frame's last work: sm_ev is recorded
   // behind every record launch (smoothing on only) and quiesce waits for it while sm_pending.
-  // The read-out's scratch -- class counts, block sums, marks, result rows with their pinned
+  // The read-out's scratch -- marks with the class counts at their head, block sums, result rows with their pinned
   // landing buffer, the pose read-out's partials -- is its own, allocated on first use and grown
   // on demand; sm_tr_ev follows a read-out's launches (waited for while sm_tr_pending: the call
   // itself synchronises, so only after a failed one).
@@ -370,10 +369,9 @@ struct gpmdm_pf {
   hipEvent_t sm_ev = nullptr, sm_tr_ev = nullptr;
   hipStream_t sm_stream = nullptr;    // the stream of the last record launch
   bool sm_pending = false, sm_tr_pending = false;
-  int* sm_counts = nullptr;
   double *sm_part = nullptr, *sm_out = nullptr, *sm_pin = nullptr, *sm_ro_part = nullptr;
   unsigned char* sm_marks = nullptr;
-  size_t sm_counts_cap = 0, sm_part_cap = 0, sm_out_cap = 0, sm_marks_cap = 0;
+  size_t sm_part_cap = 0, sm_out_cap = 0, sm_marks_cap = 0;
   int sm_slot() const { return (int)(frame % (unsigned)(sm_L + 1)); }   // the latest frame's
   // likelihood finish deferred into the resampling launch (single-shard small filters:
   // k_small_resample computes ll first, one launch less per frame); flush_ll runs it for
@@ -600,6 +598,8 @@ struct gpmdm_pf {
   // turns it off (A/B).
   bool preswitch = true;
   bool preswitched = false;           // launched, not yet consumed by gpmdm_pf_switch
+  // between switch and resample: a step is under way (a pending pre-switch is not one)
+  bool mid_step() const { return (switched && !preswitched) || dyn_done || propagated; }
   // after the pre-switch: recorded on sw_stream only when another stream or the host must
   // wait for it (an event record between two kernels idles the GPU ~6 us; on the stream
   // itself the order already holds), so it covers whatever followed the pre-switch there too
@@ -704,7 +704,6 @@ struct gpmdm_pf {
     dfree(sm_anc);
     dfree(sm_cls);
     dfree(sm_X);
-    dfree(sm_counts);
     dfree(sm_part);
     dfree(sm_out);
     dfree(sm_ro_part);
@@ -790,9 +789,9 @@ struct FcTables {
   int* seg_out() const { return t + 160; }
   int* seg_tiles() const { return t + 200; }
 };
-// the roll-out's grouping and dynamics-tile launches (capi_forecast.hip), shared with the banks'
-void fc_group(gpmdm_pf* pf, const int* cls, hipStream_t s);
-void fc_tiles(gpmdm_pf* pf, const double* X, hipStream_t s);
+// the pose read-out over the F clouds at X (F x Pf x d) into out (F x {mean[D], spread[D]});
+// capi_forecast.hip
+ReadoutParams rollout_readout(const gpmdm_pf* pf, const double* X, double* part, double* out);
 int sm_set(gpmdm_pf* pf, int lag);     // (set_smoothing of a checked handle, single or bank)
 // staging of a forecast's per-step clouds may take this much device memory (H x P x (d + 1)
 // doubles); so may the smoothing ring, and a smoothed read-out's staging of the particle rows

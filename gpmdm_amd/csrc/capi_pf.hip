@@ -729,8 +729,7 @@ int gpmdm_pf_set_obs_mask(gpmdm_pf_t pf, const uint8_t* observed) {
 
 int gpmdm_bank_set_obs_masks(gpmdm_pf_t pf, const uint8_t* observed) {
   CHECK(pf, "null handle");
-  if ((pf->switched && !pf->preswitched) || pf->dyn_done || pf->propagated)
-    return fail(GPMDM_E_STATE, "set_obs_mask between switch and resample");
+  if (pf->mid_step()) return fail(GPMDM_E_STATE, "set_obs_mask between switch and resample");
   gpmdm_model* m = pf->m;
   const size_t n = (size_t)m->D * pf->F;
   if (!observed) {

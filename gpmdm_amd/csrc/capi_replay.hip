@@ -68,8 +68,7 @@ int gpmdm_pf_stage_normals(gpmdm_pf_t pf, const double* normals, int64_t begin, 
 int gpmdm_pf_preswitch(gpmdm_pf_t pf, const double* E, void* stream) {
   CHECK(pf, "null handle");
   if (!pf->initialised) return fail(GPMDM_E_STATE, "particle filter not initialised");
-  if ((pf->switched && !pf->preswitched) || pf->dyn_done || pf->propagated)
-    return fail(GPMDM_E_STATE, "preswitch inside a step");
+  if (pf->mid_step()) return fail(GPMDM_E_STATE, "preswitch inside a step");
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipSetDevice(pf->m->device));
   if (pf->rng_mode == GPMDM_RNG_PHILOX) {

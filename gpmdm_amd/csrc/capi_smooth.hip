@@ -1,8 +1,10 @@
 // C ABI, fixed-lag smoothing (gpmdm_pf_set_smoothing, gpmdm_pf_smoothing_depth,
-// gpmdm_pf_smoothed): the ring of per-frame {ancestors, classes, states} that every resample of
-// an enabled filter records into, and the read-out that walks it -- a clear, the trace, the
-// per-lag reduce and per lag with a pose the read-out of obs_readout.h on the traced cloud, all
-// queued on the caller's stream, then one copy-back and one wait.  Kernels: smooth.h.
+// gpmdm_pf_smoothed and the banks' gpmdm_bank_set_smoothing, gpmdm_bank_smoothed): the ring of
+// per-frame {ancestors, classes, states} that every resample of an enabled filter or bank records
+// into, and the read-out that walks it -- a clear, the trace, the per-(lag, filter) reduce and
+// per lag with a pose one read-out of obs_readout.h over the F traced clouds, all queued on the
+// caller's stream, then one copy-back and one wait.  Every device result is lag-major, then
+// filter-major.  Kernels: smooth.h.
 #include "capi_internal.h"
 #include "smooth.h"
 
@@ -65,8 +67,7 @@ int sm_clear(gpmdm_pf* pf, hipStream_t s) {
 // gpmdm_pf_set_smoothing / gpmdm_bank_set_smoothing on a checked handle (P: all F x Pf particles)
 int sm_set(gpmdm_pf* pf, int lag) {
   CHECK(lag >= 0 && lag <= GPMDM_SMOOTH_MAX_LAG, "lag must be in [0, GPMDM_SMOOTH_MAX_LAG]");
-  if ((pf->switched && !pf->preswitched) || pf->dyn_done || pf->propagated)
-    return fail(GPMDM_E_STATE, "set_smoothing between switch and resample");
+  if (pf->mid_step()) return fail(GPMDM_E_STATE, "set_smoothing between switch and resample");
   gpmdm_model* m = pf->m;
   CHECK(lag == 0 || ring_bytes(pf->P, m->d, lag) <= kSmoothBytes,
         "the history of this lag needs more than 1 GiB of device memory ((lag + 1) x P x (d + 1) doubles)");
@@ -95,59 +96,42 @@ int sm_set(gpmdm_pf* pf, int lag) {
   return sm_clear(pf, ls);
 }
 
-}  // namespace gpmdm::capi
-
-extern "C" {
-
-int gpmdm_pf_set_smoothing(gpmdm_pf_t pf, int lag) {
-  CHECK(pf, "null handle");
-  CHECK(pf->F == 1, "smoothing serves single filters, not banks (gpmdm_bank_set_smoothing)");
-  return sm_set(pf, lag);
-}
-
-int gpmdm_pf_smoothing_depth(gpmdm_pf_t pf, int* lag, int* depth) {
-  CHECK(pf, "null handle");
-  if (lag) *lag = pf->sm_L;
-  if (depth) *depth = pf->sm_depth;
-  return GPMDM_OK;
-}
-
-int gpmdm_pf_smoothed(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_smoothed_out* out, void* stream) {
-  CHECK(pf, "null handle");
-  CHECK(pf->F == 1, "smoothing serves single filters, not banks (gpmdm_bank_smoothed)");
-  CHECK(pf->sm_L > 0, "smoothing is off (gpmdm_pf_set_smoothing)");
+// gpmdm_pf_smoothed / gpmdm_bank_smoothed on a checked handle with smoothing on.  stage_refusal:
+// the entry point's wording of the 1 GiB staging limit.
+static int smoothed(gpmdm_pf* pf, int lag_first, int lag_last, const gpmdm_smoothed_out* out, void* stream,
+                    const char* stage_refusal) {
   if (!pf->initialised) return fail(GPMDM_E_STATE, "particle filter not initialised");
   // (a pending pre-switch reads the cloud and writes the step's tables: neither is the smoother's)
-  if ((pf->switched && !pf->preswitched) || pf->dyn_done || pf->propagated)
-    return fail(GPMDM_E_STATE, "smoothed between switch and resample");
+  if (pf->mid_step()) return fail(GPMDM_E_STATE, "smoothed between switch and resample");
   CHECK(lag_first >= 0 && lag_first <= lag_last, "lags: 0 <= lag_first <= lag_last");
   CHECK(lag_last <= pf->sm_depth, "lag_last is above the recorded depth (gpmdm_pf_smoothing_depth)");
   gpmdm_model* m = pf->m;
   HIPCHK(hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
-  const int C = m->C, d = m->d, D = m->D;
-  const long long P = pf->P;
+  const int C = m->C, d = m->d, D = m->D, F = pf->F;
+  const long long P = pf->P, Pf = pf->Pf;
   const int n = lag_last - lag_first + 1;
-  const int W = C + d + 1 + 2 * D;
-  const long long nb = sm_blocks(P), ldm = sm_ld_marks(P);
+  const size_t n_rows = (size_t)n * F;   // row q = (l - lag_first) * F + f
+  const int W = C + d + 1;
+  const long long nbf = sm_blocks(Pf), ldm = sm_ld_marks(Pf);
   static const gpmdm_smoothed_out none{};
   const gpmdm_smoothed_out& o = out ? *out : none;
   const bool obs = o.obs_mean || o.obs_spread;
   const bool want_X = obs || o.states;
-  const size_t cnt_bytes = ((size_t)n * C * sizeof(int) + 15) & ~(size_t)15;   // counts, then the marks
-  const size_t stage = (size_t)n * ((size_t)ldm + (size_t)P * ((want_X ? sizeof(double) * d : 0) +
+  const size_t cnt_bytes = (n_rows * C * sizeof(int) + 15) & ~(size_t)15;   // counts, then the marks
+  const size_t stage = n_rows * (size_t)ldm + (size_t)n * P * ((want_X ? sizeof(double) * d : 0) +
                                                                (o.ancestors ? sizeof(int) : 0) +
-                                                               (o.classes ? sizeof(int) : 0)));
-  CHECK(stage <= kSmoothBytes, "these lags need more than 1 GiB of device staging (rows of P states, ancestors, "
-                               "classes and marks per lag): ask for fewer lags per call");
-  TRY(grow(pf->sm_marks, pf->sm_marks_cap, cnt_bytes + (size_t)n * ldm, s));
-  TRY(grow(pf->sm_part, pf->sm_part_cap, (size_t)n * nb * d, s));
-  if (pf->sm_out_cap < (size_t)n * W) {
+                                                               (o.classes ? sizeof(int) : 0));
+  CHECK(stage <= kSmoothBytes, stage_refusal);
+  TRY(grow(pf->sm_marks, pf->sm_marks_cap, cnt_bytes + n_rows * ldm, s));
+  TRY(grow(pf->sm_part, pf->sm_part_cap, n_rows * nbf * d, s));
+  const size_t n_out = n_rows * W + n_rows * 2 * D;   // the rows, then {mean[D], spread[D]} of every row
+  if (pf->sm_out_cap < n_out) {
     hfree(pf->sm_pin);
-    TRY(grow(pf->sm_out, pf->sm_out_cap, (size_t)n * W, s));
-    TRY(halloc(&pf->sm_pin, (size_t)n * W, 0));
+    TRY(grow(pf->sm_out, pf->sm_out_cap, n_out, s));
+    TRY(halloc(&pf->sm_pin, n_out, 0));
   }
-  if (obs && !pf->sm_ro_part) TRY(dalloc(&pf->sm_ro_part, readout_part_doubles(P, D)));
+  if (obs && !pf->sm_ro_part) TRY(dalloc(&pf->sm_ro_part, readout_part_doubles(Pf, D, F)));
   // per-call staging of the particle rows, released in the stream's order on every exit
   double* stage_X = nullptr;
   int *stage_anc = nullptr, *stage_cls = nullptr;
@@ -156,14 +140,16 @@ int gpmdm_pf_smoothed(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_sm
   if (rc == GPMDM_OK && o.ancestors) rc = dalloc(&stage_anc, (size_t)n * P);
   if (rc == GPMDM_OK && o.classes) rc = dalloc(&stage_cls, (size_t)n * P);
   std::vector<int> a32, c32;
+  double* out_ro = pf->sm_out + n_rows * W;
   auto launches = [&]() -> int {
     // the record of the latest frame, if it ran on another stream
     if (pf->sm_pending && pf->sm_stream != s) HIPCHK(hipStreamWaitEvent(s, pf->sm_ev, 0));
     int* counts = reinterpret_cast<int*>(pf->sm_marks);
     unsigned char* marks = pf->sm_marks + cnt_bytes;
-    HIPCHK(hipMemsetAsync(pf->sm_marks, 0, cnt_bytes + (size_t)n * ldm, s));
+    HIPCHK(hipMemsetAsync(pf->sm_marks, 0, cnt_bytes + n_rows * ldm, s));
     SmTraceArgs ta{};
-    ta.P = P;
+    ta.Pf = Pf;
+    ta.F = F;
     ta.C = C;
     ta.d = d;
     ta.lag_first = lag_first;
@@ -178,35 +164,21 @@ int gpmdm_pf_smoothed(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_sm
     ta.X_out = stage_X;
     launch_sm_trace(ta, s);
     SmReduceArgs ra{};
-    ra.P = P;
+    ra.Pf = Pf;
     ra.C = C;
     ra.d = d;
-    ra.nb = (int)nb;
+    ra.nbf = (int)nbf;
     ra.counts = counts;
     ra.partials = pf->sm_part;
     ra.marks = marks;
     ra.ld_marks = ldm;
     ra.out = pf->sm_out;
     ra.ld_out = W;
-    launch_sm_reduce(ra, n, s);
-    for (int r = 0; obs && r < n; ++r) {   // each lag's pose: the read-out on its traced cloud
-      ReadoutParams rp{};
-      rp.X = stage_X + (size_t)r * P * d;
-      rp.P = P;
-      rp.F = 1;
-      rp.d = d;
-      rp.D = D;
-      rp.ls = m->y_ls_dev;
-      rp.Xrec = m->obs.Xrec;
-      rp.nks = ksteps((int)m->N);
-      rp.Bro = m->ro_beta;
-      rp.n_groups = readout_groups(D);
-      rp.part = pf->sm_ro_part;
-      rp.out = pf->sm_out + (size_t)r * W + C + d + 1;   // {mean[D], spread[D]} of row r
-      launch_obs_readout(rp, s);
-    }
+    launch_sm_reduce(ra, n, F, s);
+    for (int r = 0; obs && r < n; ++r)   // each lag's pose: one read-out over the F traced clouds
+      launch_obs_readout(rollout_readout(pf, stage_X + (size_t)r * P * d, pf->sm_ro_part, out_ro + (size_t)r * F * 2 * D), s);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(pf->sm_pin, pf->sm_out, sizeof(double) * n * W, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pf->sm_pin, pf->sm_out, sizeof(double) * (obs ? n_out : n_rows * W), hipMemcpyDeviceToHost, s));
     if (o.states) HIPCHK(hipMemcpyAsync(o.states, stage_X, sizeof(double) * n * P * d, hipMemcpyDeviceToHost, s));
     if (o.ancestors) {
       a32.resize((size_t)n * P);
@@ -227,17 +199,58 @@ int gpmdm_pf_smoothed(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_sm
   HIPCHK(hipStreamSynchronize(s));
   pf->sm_tr_pending = false;
   if (pf->sm_pending && pf->sm_stream == s) pf->sm_pending = false;   // (the record preceded the trace on s)
-  for (int r = 0; r < n; ++r) {
-    const double* row = pf->sm_pin + (size_t)r * W;
-    if (o.class_prob) std::memcpy(o.class_prob + (size_t)r * C, row, sizeof(double) * C);
-    if (o.state_mean) std::memcpy(o.state_mean + (size_t)r * d, row + C, sizeof(double) * d);
-    if (o.distinct) o.distinct[r] = (int64_t)row[C + d];
-    if (o.obs_mean) std::memcpy(o.obs_mean + (size_t)r * D, row + C + d + 1, sizeof(double) * D);
-    if (o.obs_spread) std::memcpy(o.obs_spread + (size_t)r * D, row + C + d + 1 + D, sizeof(double) * D);
+  const double* ro = pf->sm_pin + n_rows * W;
+  for (size_t q = 0; q < n_rows; ++q) {
+    const double* row = pf->sm_pin + q * W;
+    if (o.class_prob) std::memcpy(o.class_prob + q * C, row, sizeof(double) * C);
+    if (o.state_mean) std::memcpy(o.state_mean + q * d, row + C, sizeof(double) * d);
+    if (o.distinct) o.distinct[q] = (int64_t)row[C + d];
+    if (o.obs_mean) std::memcpy(o.obs_mean + q * D, ro + q * 2 * D, sizeof(double) * D);
+    if (o.obs_spread) std::memcpy(o.obs_spread + q * D, ro + q * 2 * D + D, sizeof(double) * D);
   }
   for (size_t i = 0; i < a32.size(); ++i) o.ancestors[i] = a32[i];
   for (size_t i = 0; i < c32.size(); ++i) o.classes[i] = c32[i];
   return GPMDM_OK;
+}
+
+}  // namespace gpmdm::capi
+
+extern "C" {
+
+int gpmdm_pf_set_smoothing(gpmdm_pf_t pf, int lag) {
+  CHECK(pf, "null handle");
+  CHECK(pf->F == 1, "smoothing serves single filters, not banks (gpmdm_bank_set_smoothing)");
+  return sm_set(pf, lag);
+}
+
+int gpmdm_bank_set_smoothing(gpmdm_pf_t pf, int lag) {
+  CHECK(pf, "null handle");
+  return sm_set(pf, lag);
+}
+
+int gpmdm_pf_smoothing_depth(gpmdm_pf_t pf, int* lag, int* depth) {
+  CHECK(pf, "null handle");
+  if (lag) *lag = pf->sm_L;
+  if (depth) *depth = pf->sm_depth;
+  return GPMDM_OK;
+}
+
+int gpmdm_pf_smoothed(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_smoothed_out* out, void* stream) {
+  CHECK(pf, "null handle");
+  CHECK(pf->F == 1, "smoothing serves single filters, not banks (gpmdm_bank_smoothed)");
+  CHECK(pf->sm_L > 0, "smoothing is off (gpmdm_pf_set_smoothing)");
+  return smoothed(pf, lag_first, lag_last, out, stream,
+                  "these lags need more than 1 GiB of device staging (rows of P states, ancestors, classes and "
+                  "marks per lag): ask for fewer lags per call");
+}
+
+int gpmdm_bank_smoothed(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_smoothed_out* out, void* stream) {
+  CHECK(pf, "null handle");
+  CHECK(pf->F <= 65535, "bank smoothing serves up to 65535 filters");
+  CHECK(pf->sm_L > 0, "smoothing is off (gpmdm_bank_set_smoothing)");
+  return smoothed(pf, lag_first, lag_last, out, stream,
+                  "these lags need more than 1 GiB of device staging (rows of F x P states, ancestors, classes and "
+                  "marks per lag): ask for fewer lags per call");
 }
 
 }  // extern "C"

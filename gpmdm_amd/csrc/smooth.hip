@@ -17,7 +17,8 @@ __global__ __launch_bounds__(kB) void k_sm_record(SmRecordArgs a) {
 }
 
 // ---------------------------------------------------------------------------------
-// Thread p walks its ancestry; the block moves through the lags together (the same trip count
+// Thread p of filter f = blockIdx.y walks its ancestry through filter f's rows of each slot
+// (every index in-filter); the block moves through the lags together (the same trip count
 // for every thread, dead threads included: they add zeros), so each lag's class counts go
 // through a block histogram in LDS to one integer atomic per class and block, and its state
 // sums through the wave butterflies and then the four waves in order to partials[row][block].
@@ -25,29 +26,30 @@ __global__ __launch_bounds__(kB) void k_sm_trace(SmTraceArgs a) {
   __shared__ double red[kB / 64][kMaxD];
   __shared__ int hist[kMaxClasses];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const long long f = blockIdx.y, nbf = gridDim.x;
   const long long p = (long long)blockIdx.x * kB + tid;
-  const bool live = p < a.P;
+  const bool live = p < a.Pf;
   const int d = a.d, ns = a.ring.n_slots;
-  const long long nb = gridDim.x;
+  const long long P = a.Pf * a.F;
   long long j = live ? p : 0;
   int slot = a.ring.head;
   for (int l = 0; l <= a.lag_last; ++l) {
-    const long long row = (long long)slot * a.P;
+    const long long row = (long long)slot * P + f * a.Pf;
     if (l >= a.lag_first) {
-      const long long r = l - a.lag_first;
+      const long long q = (long long)(l - a.lag_first) * a.F + f;
       if (tid < a.C) hist[tid] = 0;
       __syncthreads();
       if (live) {
         int c = a.ring.cls[row + j];
         c = c < 0 ? 0 : (c >= a.C ? a.C - 1 : c);
         atomicAdd(&hist[c], 1);
-        a.marks[r * a.ld_marks + j] = 1;
-        if (a.anc_out) a.anc_out[r * a.P + p] = (int)j;
-        if (a.cls_out) a.cls_out[r * a.P + p] = c;
+        a.marks[q * a.ld_marks + j] = 1;
+        if (a.anc_out) a.anc_out[q * a.Pf + p] = (int)j;
+        if (a.cls_out) a.cls_out[q * a.Pf + p] = c;
       }
       for (int k = 0; k < d; ++k) {
         const double x = live ? a.ring.X[(row + j) * d + k] : 0.0;
-        if (live && a.X_out) a.X_out[(r * a.P + p) * d + k] = x;
+        if (live && a.X_out) a.X_out[(q * a.Pf + p) * d + k] = x;
         const double s = wave_sum(x);
         if (lane == 0) red[w][k] = s;
       }
@@ -55,15 +57,15 @@ __global__ __launch_bounds__(kB) void k_sm_trace(SmTraceArgs a) {
       if (tid < d) {
         double t = red[0][tid];
         for (int v = 1; v < kB / 64; ++v) t += red[v][tid];
-        a.partials[(r * nb + blockIdx.x) * d + tid] = t;
+        a.partials[(q * nbf + blockIdx.x) * d + tid] = t;
       }
-      if (tid < a.C && hist[tid]) atomicAdd(&a.counts[r * a.C + tid], hist[tid]);
+      if (tid < a.C && hist[tid]) atomicAdd(&a.counts[q * a.C + tid], hist[tid]);
       __syncthreads();
     }
     if (l < a.lag_last) {
       if (live) {
         const long long n = a.ring.anc[row + j];
-        j = n < 0 ? 0 : (n >= a.P ? a.P - 1 : n);   // (ridx is in [0, P): never a wild gather)
+        j = n < 0 ? 0 : (n >= a.Pf ? a.Pf - 1 : n);   // (ridx is in [0, Pf): never a wild gather)
       }
       slot = slot == 0 ? ns - 1 : slot - 1;
     }
@@ -71,34 +73,34 @@ __global__ __launch_bounds__(kB) void k_sm_trace(SmTraceArgs a) {
 }
 
 // ---------------------------------------------------------------------------------
-// One workgroup per lag row: class fractions (the count divided once), the mean state from
-// the blocks' sums (thread-strided, wave butterfly, waves in order: k_fc_reduce's order), and
+// One workgroup per (lag, filter), row q = lag row * F + f: class fractions (the count divided
+// once by Pf), the mean state from the blocks' sums (thread-strided, wave butterfly, waves in order: k_fc_reduce's order), and
 // the number of marks (bytes of 0 / 1, four to a word: their sum is the word's popcount).
 __global__ __launch_bounds__(kB) void k_sm_reduce(SmReduceArgs a) {
   __shared__ double red[kB / 64];
   __shared__ unsigned long long cnt[kB / 64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const long long r = blockIdx.x;
-  double* out = a.out + r * a.ld_out;
-  if (tid < a.C) out[tid] = (double)a.counts[r * a.C + tid] / (double)a.P;
-  const double* part = a.partials + r * a.nb * a.d;
+  const long long q = (long long)blockIdx.x * gridDim.y + blockIdx.y;
+  double* out = a.out + q * a.ld_out;
+  if (tid < a.C) out[tid] = (double)a.counts[q * a.C + tid] / (double)a.Pf;
+  const double* part = a.partials + q * a.nbf * a.d;
   for (int j = 0; j < a.d; ++j) {
     double s = 0.0;
-    for (int b = tid; b < a.nb; b += kB) s += part[(long long)b * a.d + j];
+    for (int b = tid; b < a.nbf; b += kB) s += part[(long long)b * a.d + j];
     s = wave_sum(s);
     if (lane == 0) red[w] = s;
     __syncthreads();
     if (tid == 0) {
       double t = red[0];
       for (int v = 1; v < kB / 64; ++v) t += red[v];
-      out[a.C + j] = t / (double)a.P;
+      out[a.C + j] = t / (double)a.Pf;
     }
     __syncthreads();
   }
-  const uint4* m = reinterpret_cast<const uint4*>(a.marks + r * a.ld_marks);   // rows are 16-byte multiples
+  const uint4* m = reinterpret_cast<const uint4*>(a.marks + q * a.ld_marks);   // rows are 16-byte multiples
   unsigned long long n = 0;
-  for (long long q = tid; q < a.ld_marks / 16; q += kB) {
-    const uint4 v = m[q];
+  for (long long i = tid; i < a.ld_marks / 16; i += kB) {
+    const uint4 v = m[i];
     n += __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
   }
 #pragma unroll
@@ -120,10 +122,10 @@ void launch_sm_record(const SmRecordArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_sm_record, dim3(nblk(n, kB)), dim3(kB), 0, s, a);
 }
 void launch_sm_trace(const SmTraceArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_sm_trace, dim3(nblk(a.P, kB)), dim3(kB), 0, s, a);
+  hipLaunchKernelGGL(k_sm_trace, dim3(nblk(a.Pf, kB), (unsigned)a.F), dim3(kB), 0, s, a);
 }
-void launch_sm_reduce(const SmReduceArgs& a, int n_lags, hipStream_t s) {
-  hipLaunchKernelGGL(k_sm_reduce, dim3((unsigned)n_lags), dim3(kB), 0, s, a);
+void launch_sm_reduce(const SmReduceArgs& a, int n_lags, int F, hipStream_t s) {
+  hipLaunchKernelGGL(k_sm_reduce, dim3((unsigned)n_lags, (unsigned)F), dim3(kB), 0, s, a);
 }
 
 }  // namespace gpmdm

@@ -137,6 +137,63 @@ def _check_lag_range(lag):
     return one(lag), one(lag)
 
 
+def _forecast_call(owner, entry, filters, horizon, mode, observation, particles, seed):
+    """``forecast`` of a filter (``filters`` = ()) or a bank ((F_local,)): the argument checks, then
+    the library's ``entry`` (its name; None for a bank without local filters) into host arrays
+    with the library's leading shape (H, *filters).  Returns the six arrays in ``Forecast``'s
+    order, None for those not asked for."""
+    if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)):
+        raise ValueError(f"horizon must be an integer, got {horizon!r}")
+    H = int(horizon)
+    if not 1 <= H <= _lib.GPMDM_FORECAST_MAX_HORIZON:
+        raise ValueError(f"horizon must be in [1, {_lib.GPMDM_FORECAST_MAX_HORIZON}], got {H}")
+    if mode not in _lib.FORECAST_MODES:
+        raise ValueError(f"mode must be one of {sorted(_lib.FORECAST_MODES)}, got {mode!r}")
+    P, C, d, D = owner._num_particles, owner.num_classes, owner.latent_dim, owner.observation_dim
+    lead = (H, *filters)
+    cp, sm = np.zeros(lead + (C,)), np.zeros(lead + (d,))
+    om = np.zeros(lead + (D,)) if observation else None
+    osp = np.zeros(lead + (D,)) if observation else None
+    st = np.zeros(lead + (P, d)) if particles else None
+    cl = np.zeros(lead + (P,), dtype=np.int64) if particles else None
+    if entry is not None:
+        owner._sync_model()
+        out = _lib.ForecastOut(_lib.dptr(cp), _lib.dptr(sm), _lib.dptr(om), _lib.dptr(osp), _lib.dptr(st),
+                               _lib.i64ptr(cl))
+        sd = None if seed is None else ctypes.byref(ctypes.c_uint64(int(seed) & (2 ** 64 - 1)))
+        _lib.check(getattr(_lib.load(), entry)(owner._h, H, _lib.FORECAST_MODES[mode], sd, ctypes.byref(out),
+                                               owner._stream()), "forecast")
+    return cp, sm, om, osp, st, cl
+
+
+def _smoothed_call(owner, what, entry, filters, lag, observation, particles):
+    """``smoothed`` of a filter (``filters`` = ()) or a bank ((F_local,)), ``what`` its name in the
+    messages: the argument checks, then the library's ``entry`` (its name; None for a bank without
+    local filters) into host arrays with the library's leading shape (n, *filters).  Returns the
+    lags and the eight arrays that follow ``frames`` in ``Smoothed``, None for those not asked for."""
+    first, last = _check_lag_range(lag)
+    if not owner._smoothing_lag:
+        raise ValueError(f"smoothing is off: build the {what} with smoothing_lag=L or call set_smoothing(L)")
+    depth = owner.smoothing_depth
+    if last is None:
+        last = depth
+    if last > depth:
+        raise ValueError(f"lag {last} is above the recorded depth {depth} (smoothing lag {owner._smoothing_lag})")
+    P, C, d, D = owner._num_particles, owner.num_classes, owner.latent_dim, owner.observation_dim
+    lead = (last - first + 1, *filters)
+    cp, sm, da = np.zeros(lead + (C,)), np.zeros(lead + (d,)), np.zeros(lead, dtype=np.int64)
+    om = np.zeros(lead + (D,)) if observation else None
+    osp = np.zeros(lead + (D,)) if observation else None
+    an = np.zeros(lead + (P,), dtype=np.int64) if particles else None
+    st = np.zeros(lead + (P, d)) if particles else None
+    cl = np.zeros(lead + (P,), dtype=np.int64) if particles else None
+    if entry is not None:
+        out = _lib.SmoothedOut(_lib.dptr(cp), _lib.dptr(sm), _lib.i64ptr(da), _lib.dptr(om), _lib.dptr(osp),
+                               _lib.i64ptr(an), _lib.dptr(st), _lib.i64ptr(cl))
+        _lib.check(getattr(_lib.load(), entry)(owner._h, first, last, ctypes.byref(out), owner._stream()), "smoothed")
+    return np.arange(first, last + 1, dtype=np.int64), (cp, sm, da, om, osp, an, st, cl)
+
+
 def _as_f64_vector(z) -> np.ndarray:
     """The observation as a contiguous float64 vector (the reference casts it with
     torch.tensor(z, dtype=float64), gpmdm_pf.py:123; float32 -> float64 is exact)."""
@@ -614,27 +671,9 @@ class GPMDM_PF:
         longer one.  The filter is not changed: no state change, no draw from torch's
         generator, and later updates are bitwise those without the call.  A sharded filter
         forecasts its replicated cloud on rank 0."""
-        if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)):
-            raise ValueError(f"horizon must be an integer, got {horizon!r}")
-        H = int(horizon)
-        if not 1 <= H <= _lib.GPMDM_FORECAST_MAX_HORIZON:
-            raise ValueError(f"horizon must be in [1, {_lib.GPMDM_FORECAST_MAX_HORIZON}], got {H}")
-        if mode not in _lib.FORECAST_MODES:
-            raise ValueError(f"mode must be one of {sorted(_lib.FORECAST_MODES)}, got {mode!r}")
-        self._sync_model()
-        P, C, d, D = self._num_particles, self.num_classes, self.latent_dim, self.observation_dim
-        cp, sm = np.zeros((H, C)), np.zeros((H, d))
-        om = np.zeros((H, D)) if observation else None
-        osp = np.zeros((H, D)) if observation else None
-        st = np.zeros((H, P, d)) if particles else None
-        cl = np.zeros((H, P), dtype=np.int64) if particles else None
-        out = _lib.ForecastOut(_lib.dptr(cp), _lib.dptr(sm), _lib.dptr(om), _lib.dptr(osp), _lib.dptr(st),
-                               _lib.i64ptr(cl))
-        sd = None if seed is None else ctypes.byref(ctypes.c_uint64(int(seed) & (2 ** 64 - 1)))
-        _lib.check(_lib.load().gpmdm_pf_forecast(self._h, H, _lib.FORECAST_MODES[mode], sd, ctypes.byref(out),
-                                                 self._stream()), "forecast")
         t = lambda a: None if a is None else torch.from_numpy(a)   # noqa: E731
-        return Forecast(t(cp), t(sm), t(om), t(osp), t(st), t(cl))
+        return Forecast(*map(t, _forecast_call(self, "gpmdm_pf_forecast", (), horizon, mode, observation,
+                                               particles, seed)))
 
     def set_smoothing(self, lag: int):
         """Keep the last ``lag`` + 1 frames' resampling ancestors, classes and states on the
@@ -685,29 +724,9 @@ class GPMDM_PF:
         draw, no state change, and later updates are bitwise those without the call; the same
         history gives bitwise the same result.  A sharded filter reads rank 0's history (every
         rank records the replicated cloud).  Needs ``smoothing_lag`` / ``set_smoothing``."""
-        first, last = _check_lag_range(lag)
-        if not self._smoothing_lag:
-            raise ValueError("smoothing is off: build the filter with smoothing_lag=L or call set_smoothing(L)")
-        depth = self.smoothing_depth
-        if last is None:
-            last = depth
-        if last > depth:
-            raise ValueError(f"lag {last} is above the recorded depth {depth} (smoothing lag {self._smoothing_lag})")
-        P, C, d, D = self._num_particles, self.num_classes, self.latent_dim, self.observation_dim
-        n = last - first + 1
-        cp, sm, da = np.zeros((n, C)), np.zeros((n, d)), np.zeros(n, dtype=np.int64)
-        om = np.zeros((n, D)) if observation else None
-        osp = np.zeros((n, D)) if observation else None
-        an = np.zeros((n, P), dtype=np.int64) if particles else None
-        st = np.zeros((n, P, d)) if particles else None
-        cl = np.zeros((n, P), dtype=np.int64) if particles else None
-        out = _lib.SmoothedOut(_lib.dptr(cp), _lib.dptr(sm), _lib.i64ptr(da), _lib.dptr(om), _lib.dptr(osp),
-                               _lib.i64ptr(an), _lib.dptr(st), _lib.i64ptr(cl))
-        _lib.check(_lib.load().gpmdm_pf_smoothed(self._h, first, last, ctypes.byref(out), self._stream()),
-                   "smoothed")
-        lags = np.arange(first, last + 1, dtype=np.int64)
+        lags, rest = _smoothed_call(self, "filter", "gpmdm_pf_smoothed", (), lag, observation, particles)
         t = lambda a: None if a is None else torch.from_numpy(a)   # noqa: E731
-        return Smoothed(t(lags), t(self.frame - lags), t(cp), t(sm), t(da), t(om), t(osp), t(an), t(st), t(cl))
+        return Smoothed(t(lags), t(self.frame - lags), *map(t, rest))
 
     @property
     def frame(self) -> int:

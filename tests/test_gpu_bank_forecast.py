@@ -1,4 +1,4 @@
-"""GPU: ``GPMDM_PF_Bank.forecast`` (gpmdm_bank_forecast, csrc/bank_rollout.h).
+"""GPU: ``GPMDM_PF_Bank.forecast`` (gpmdm_bank_forecast, csrc/forecast.h).
 
 The bank changes the schedule, not the numbers: row f of every field is bitwise
 ``GPMDM_PF(rng='philox', seed=seed + f).forecast(H, seed=seed + f)`` of a single filter that

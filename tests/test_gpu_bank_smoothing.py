@@ -1,6 +1,6 @@
 """GPU: fixed-lag smoothing for filter banks (``GPMDM_PF_Bank(smoothing_lag=...)``,
 ``set_smoothing``, ``smoothed``; gpmdm_bank_set_smoothing, gpmdm_bank_smoothed,
-csrc/bank_rollout.h).
+csrc/smooth.h).
 
 Every filter of the bank is checked twice: against ``smooth_ref`` on the bank's own per-frame
 exports with test_gpu_smoothing.py's ``_check`` (ancestors, classes, states and distinct counts

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Cost of forecasts and fixed-lag smoothing in a filter bank (GPMDM_PF_Bank.forecast, smoothed;
-gpmdm_bank_forecast, gpmdm_bank_smoothed, csrc/bank_rollout.h).
+gpmdm_bank_forecast, gpmdm_bank_smoothed, csrc/forecast.h, csrc/smooth.h).
 
 On one GPU, Philox, after 5 warm-up frames, three repeats of every figure (the median is
 reported, all three are kept), for the notebook bank (config 1: N = 500, F = 39, Pf = 100) and
