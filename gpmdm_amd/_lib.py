@@ -63,6 +63,13 @@ class SmoothedOut(ctypes.Structure):
                 ("obs_spread", _dp), ("ancestors", _i64p), ("states", _dp), ("classes", _i64p)]
 
 
+class InnovationOut(ctypes.Structure):
+    """gpmdm_innovation_out: host arrays, any may be NULL."""
+    _fields_ = [("mean", _dp), ("spread", _dp), ("gp_variance", _dp), ("variance", _dp), ("residual", _dp),
+                ("zscore", _dp), ("log_density", _dp), ("n_valid", _i64p), ("observed", c_void_p),
+                ("states", _dp), ("variance_common", _dp)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "gpmdm_model_create": (c_int, [POINTER(ModelDesc), c_int, POINTER(c_void_p)]),
@@ -122,6 +129,12 @@ _SIGS = {
     "gpmdm_bank_forecast": (c_int, [c_void_p, c_int, c_int, POINTER(c_uint64), POINTER(ForecastOut), c_void_p]),
     "gpmdm_bank_set_smoothing": (c_int, [c_void_p, c_int]),
     "gpmdm_bank_smoothed": (c_int, [c_void_p, c_int, c_int, POINTER(SmoothedOut), c_void_p]),
+    "gpmdm_pf_set_predictive": (c_int, [c_void_p, c_int]),
+    "gpmdm_pf_innovation": (c_int, [c_void_p, POINTER(InnovationOut), c_void_p]),
+    "gpmdm_pf_observation_gp": (c_int, [c_void_p, _dp, c_void_p]),
+    "gpmdm_bank_set_predictive": (c_int, [c_void_p, c_int]),
+    "gpmdm_bank_innovation": (c_int, [c_void_p, POINTER(InnovationOut), c_void_p]),
+    "gpmdm_bank_observation_gp": (c_int, [c_void_p, _dp, c_void_p]),
     "gpmdm_pf_set_comm": (c_int, [c_void_p, c_void_p, c_int]),
     "gpmdm_comm_unique_id": (c_int, [c_void_p]),
     "gpmdm_comm_init": (c_int, [c_int, c_int, c_void_p, c_int, POINTER(c_void_p)]),

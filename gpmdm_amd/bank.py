@@ -28,7 +28,7 @@ import torch
 from . import _lib, replay
 from .distributed import shard_range
 from .model import GPMDM
-from .pf import Forecast, Smoothed, _check_smoothing_lag, _forecast_call, _smoothed_call
+from .pf import Forecast, Innovation, Smoothed, _check_smoothing_lag, _forecast_call, _innovation_call, _smoothed_call
 
 
 def _filter_major(a):
@@ -39,7 +39,8 @@ def _filter_major(a):
 class GPMDM_PF_Bank:
     def __init__(self, gpmdm: GPMDM, markov_switching_model, num_filters: int, num_particles: int, *,
                  seed=None, resample: str = "multinomial", process_group=None, shard=None,
-                 dedup: bool = True, dyn_tiles: str = "auto", obs_cutoff: bool = False, smoothing_lag: int = 0):
+                 dedup: bool = True, dyn_tiles: str = "auto", obs_cutoff: bool = False, smoothing_lag: int = 0,
+                 predictive: bool = False):
         self._gpmdm = gpmdm
         self._gpmdm.set_evaluation_mode()
         self._T = torch.as_tensor(markov_switching_model).type(torch.float64)
@@ -48,6 +49,7 @@ class GPMDM_PF_Bank:
         if resample not in ("multinomial", "systematic"):
             raise ValueError("resample must be 'multinomial' or 'systematic'")
         self._smoothing_lag = _check_smoothing_lag(smoothing_lag)
+        self._predictive = False
         self._num_filters = int(num_filters)
         self._num_particles = int(num_particles)
         if self._num_filters < 1 or self._num_particles < 1:
@@ -93,6 +95,8 @@ class GPMDM_PF_Bank:
             self._init_particles()
             if self._smoothing_lag:
                 self.set_smoothing(self._smoothing_lag)
+        if predictive:
+            self.set_predictive(True)
 
     def __del__(self):
         try:
@@ -275,7 +279,31 @@ class GPMDM_PF_Bank:
             _lib.check(_lib.load().gpmdm_pf_predict(self._h, _lib.dptr(out), self._stream()), "predict")
         return torch.from_numpy(out)
 
-    def current_observation(self, spread: bool = True):
+    def set_predictive(self, on: bool = True):
+        """``GPMDM_PF.set_predictive`` for the bank (gpmdm_bank_set_predictive): every update
+        from now on keeps each particle's vc for ``innovation`` and
+        ``current_observation(gp_variance=True)``; off, the bank issues exactly the work of a
+        bank built without it.  Between updates only."""
+        if self._h is not None:
+            self._sync_model()
+            _lib.check(_lib.load().gpmdm_bank_set_predictive(self._h, 1 if on else 0), "set_predictive")
+        self._predictive = bool(on)
+
+    @property
+    def predictive(self) -> bool:
+        return self._predictive
+
+    def innovation(self, particles: bool = False) -> Innovation:
+        """``GPMDM_PF.innovation`` for every local filter in one pair of launches
+        (gpmdm_bank_innovation): every field has a leading filter axis, and row f is bitwise the
+        single filter's result on filter f's frame (its own row of ``Z`` and of the masks; a
+        blacked-out filter has ``n_valid`` 0 and NaN in every field but ``mean`` and ``spread``)."""
+        if not self._predictive:
+            raise ValueError("innovation: build the bank with predictive=True or call set_predictive(True)")
+        return _innovation_call(self, None if self._h is None else "gpmdm_bank_innovation", (self.local_filters,),
+                                particles)
+
+    def current_observation(self, spread: bool = True, gp_variance: bool = False):
         """(F_local, D): the filtered pose of every local filter, ``GPMDM_PF.current_observation``
         per filter -- the observation GP's mean averaged over the particles the filter holds
         now (after masked updates: with the unseen joints imputed) and, with ``spread``, the
@@ -289,9 +317,16 @@ class GPMDM_PF_Bank:
             self._sync_model()
             _lib.check(_lib.load().gpmdm_bank_observation(self._h, _lib.dptr(mean), _lib.dptr(var), self._stream()),
                        "current_observation")
-        if spread:
-            return torch.from_numpy(mean), torch.from_numpy(var)
-        return torch.from_numpy(mean)
+        res = (torch.from_numpy(mean), torch.from_numpy(var)) if spread else (torch.from_numpy(mean),)
+        if gp_variance:                       # (GPMDM_PF.current_observation: the GP's own variance, per filter)
+            if not self._predictive:
+                raise ValueError("gp_variance: build the bank with predictive=True or call set_predictive(True)")
+            gpv = np.zeros((Fl, D))
+            if self._h is not None:
+                _lib.check(_lib.load().gpmdm_bank_observation_gp(self._h, _lib.dptr(gpv), self._stream()),
+                           "current_observation")
+            res = res + (torch.from_numpy(gpv),)
+        return res if len(res) > 1 else res[0]
 
     def current_observation_mean(self) -> torch.Tensor:
         """``current_observation``'s mean alone: (F_local, D)."""

@@ -282,6 +282,7 @@ static void launch_dyn_gemm(gpmdm_pf* pf, hipStream_t s) {
 int propagate_dynamics(gpmdm_pf* pf, const double* normals, hipStream_t s, bool zstage) {
   gpmdm_model* m = pf->m;
   const int C = m->C, d = m->d;
+  pf->pv_clear();                      // X_prop is about to be rewritten: the kept vc is no longer its
   if (pf->rng_mode == GPMDM_RNG_REPLAY) {
     CHECK(normals, "replay mode needs the dynamics normals");
     pf->n_staged_frame = pf->normals_staged(normals, (long long)pf->P * d);
@@ -574,6 +575,7 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
       oa.cut_tm = m->obs_cut.T_M;
     }
     oa.health = pf->health;
+    if (pf->predictive && pf->n_ranks == 1) oa.vc_out = pf->vc_prop;   // (null: the frame as it was)
     pf->ll_pending = false;
     pf->bmax_ready = false;
     if (pf->n_ranks == 1 && !oa.own && oa.ll_offset == 0 && small_resample_ok(norm_args(pf), resample_args(pf))) {
@@ -591,6 +593,16 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
     pf->mark_end(s, GPMDM_STAGE_OBS_FINISH, t0);
   }
   HIPCHK(hipGetLastError());
+  if (pf->predictive && pf->n_ranks == 1) {
+    // the frame's staged z stays where the tiles read it (the slot and pf->z are next written
+    // by a later frame's staging, behind that frame's propagate); the mask as weighed with
+    pf->pv_z = zsrc;
+    pf->pv_masked = masked;
+    if (masked) std::memcpy(pf->pv_mask, pf->obs_mask.data(), (size_t)D * pf->F);
+    pf->pv_has_vc = !(masked && pf->D_obs == 0) && nl > 0;
+    pf->pv_weighed = true;
+    pf->pv_resampled = false;
+  }
   pf->propagated = true;
   pf->dyn_done = false;
   return GPMDM_OK;
@@ -746,6 +758,7 @@ int gpmdm_pf_resample(gpmdm_pf_t pf, const double* uniforms, void* stream) {
   }
   pf->frame += 1;
   pf->propagated = false;
+  pf->pv_resampled = pf->pv_weighed;   // (ridx now holds the kept vc's ancestors)
   if (pf->sm_L > 0) TRY(sm_record(pf, s));   // smoothing: this frame into the ancestry ring
   if (pf->preswitch) {                 // the next frame's switch, behind the read-out
     TRY(do_switch(pf, nullptr, nullptr, s, pf->order_wanted()));

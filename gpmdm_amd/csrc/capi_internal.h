@@ -9,6 +9,8 @@
 //   capi_forecast.hip  the multi-step forecast roll-out (gpmdm_pf_forecast, gpmdm_bank_forecast)
 //   capi_smooth.hip    fixed-lag smoothing: the ancestry ring and its read-out (gpmdm_pf_smoothed,
 //                      gpmdm_bank_smoothed)
+//   capi_innov.hip     per-joint innovations and the GP's predictive variance (gpmdm_pf_set_predictive,
+//                      gpmdm_pf_innovation, gpmdm_pf_observation_gp and the banks')
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -373,6 +375,26 @@ struct gpmdm_pf {
   unsigned char* sm_marks = nullptr;
   size_t sm_part_cap = 0, sm_out_cap = 0, sm_marks_cap = 0;
   int sm_slot() const { return (int)(frame % (unsigned)(sm_L + 1)); }   // the latest frame's
+  // Innovations and the GP's predictive variance (gpmdm_pf_set_predictive, gpmdm_pf_innovation,
+  // gpmdm_pf_observation_gp and the banks'; obs_innov.h, capi_innov.hip).  predictive: every
+  // weigh keeps vc = 1 - k^T K_y^-1 k of its particles in vc_prop (F x Pf, the order of X_prop
+  // and ll), remembers where the frame's staged z lies (pv_z: pf->z or the frame's mapped
+  // staging slot -- either is next written by the staging of a later frame, which follows that
+  // frame's propagate) and the mask it was weighed with (pv_mask: mapped, F x D bytes;
+  // pv_masked).  pv_weighed: a frame has been weighed with the feature on since the last
+  // propagate, init, import, rebind or set_predictive (pv_has_vc: an observation kernel ran
+  // for it, i.e. no single-filter blackout); pv_resampled: that frame's resample has completed,
+  // so vc_prop[ridx] is the resampled cloud's.  The calls' scratch is their own, grown on
+  // demand; iv_ev follows their launches (quiesce waits for it while iv_pending).
+  bool predictive = false, pv_weighed = false, pv_has_vc = false, pv_resampled = false, pv_masked = false;
+  double* vc_prop = nullptr;
+  const double* pv_z = nullptr;
+  unsigned char *pv_mask = nullptr, *pv_mask_dev = nullptr;
+  double *iv_part = nullptr, *iv_out = nullptr, *iv_pin = nullptr;
+  size_t iv_part_cap = 0, iv_out_cap = 0;
+  hipEvent_t iv_ev = nullptr;
+  bool iv_pending = false;
+  void pv_clear() { pv_weighed = pv_has_vc = pv_resampled = false; }
   // likelihood finish deferred into the resampling launch (single-shard small filters:
   // k_small_resample computes ll first, one launch less per frame); flush_ll runs it for
   // any reader of ll that comes first
@@ -711,6 +733,12 @@ struct gpmdm_pf {
     hfree(sm_pin);
     if (sm_ev) (void)hipEventDestroy(sm_ev);
     if (sm_tr_ev) (void)hipEventDestroy(sm_tr_ev);
+    dfree(vc_prop);
+    dfree(iv_part);
+    dfree(iv_out);
+    hfree(iv_pin);
+    hfree(pv_mask);
+    if (iv_ev) (void)hipEventDestroy(iv_ev);
     dfree(bmax);
     dfree(bmax_rows);
     dfree(owner);
@@ -793,6 +821,7 @@ struct FcTables {
 // capi_forecast.hip
 ReadoutParams rollout_readout(const gpmdm_pf* pf, const double* X, double* part, double* out);
 int sm_set(gpmdm_pf* pf, int lag);     // (set_smoothing of a checked handle, single or bank)
+int iv_wait(gpmdm_pf* pf);             // an innovation call's launches in flight (capi_innov.hip)
 // staging of a forecast's per-step clouds may take this much device memory (H x P x (d + 1)
 // doubles); so may the smoothing ring, and a smoothed read-out's staging of the particle rows
 constexpr size_t kForecastStageBytes = (size_t)1 << 30;

@@ -311,6 +311,7 @@ int quiesce(gpmdm_pf* pf) {
   // a smoothing record follows the frame's read-out number on the frame's stream; a smoothed
   // read-out that failed before its own wait
   TRY(sm_wait(pf));
+  TRY(iv_wait(pf));                    // an innovation call that failed before its own wait
   return GPMDM_OK;
 }
 
@@ -425,6 +426,7 @@ int gpmdm_pf_init(gpmdm_pf_t pf, const double* states, const int64_t* classes) {
   pf->own_valid = false;               // no ancestors yet: identity ownership
   pf->rows_st = pf->rows_ll = nullptr;
   pf->switched = pf->propagated = pf->dyn_done = pf->ll_pending = pf->gemm_ahead = false;
+  pf->pv_clear();                      // no frame weighed on this cloud yet
   return sm_clear(pf, ls);             // smoothing: this cloud is the history's root
 }
 
@@ -501,6 +503,7 @@ int gpmdm_pf_import(gpmdm_pf_t pf, const double* states, const int64_t* classes,
   if (pf->seq_pin) pf->ro_seq = pf->seq_min();   // (synchronised: nothing to wait for)
   pf->initialised = true;
   pf->switched = pf->propagated = pf->dyn_done = pf->gemm_ahead = false;
+  pf->pv_clear();                      // the exporter's vc is not part of the state
   return sm_clear(pf, ls);             // smoothing: the imported cloud is the history's root
 }
 
@@ -676,6 +679,7 @@ int gpmdm_pf_set_model(gpmdm_pf_t pf, gpmdm_model_t m) {
     const std::vector<unsigned char> mask = pf->obs_mask;
     TRY(install_obs_mask(pf, mask));
   }
+  pf->pv_clear();                      // the kept vc was the old model's
   return sm_clear(pf, ls);             // smoothing: older frames were the old model's
 }
 

@@ -31,6 +31,8 @@
 // A bank (gpmdm_bank_observation) adds a filter dimension to both grids: ceil(P / 64) tiles per
 // filter, cut within the filter, partials and finish per filter -- the partition within a filter
 // is the single filter's, so row f is bitwise the read-out of a single filter holding f's cloud.
+// The K loop, the (mean, M2) epilogue and the pairwise update are device functions of
+// obs_readout_tile.h, which the innovation tile (obs_innov.h) calls too.
 #pragma once
 #include <hip/hip_runtime.h>
 

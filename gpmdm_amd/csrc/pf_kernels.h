@@ -184,6 +184,9 @@ struct ObsFinishArgs {
   long long cut_ld, cut_o0;
   const int2* cut_split;
   int cut_pt, cut_tpc, cut_tm;
+  // predictive filters (gpmdm_pf_set_predictive): vc = 1 - k^T K_y^-1 k of every output, stored at
+  // the index its ll is stored at (NaN for a blacked-out filter's outputs), or nullptr
+  double* vc_out;
 };
 
 // Normalisation and resampling run per filter: grid (nb, F), nb blocks of 256 per filter.

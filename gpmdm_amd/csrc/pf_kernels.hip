@@ -767,13 +767,21 @@ __device__ __forceinline__ double obs_ll_value(const ObsFinishArgs& a, long long
   return -0.5 * S / vc - Dn * log(vc) - sum_log_il2 - ll_const;
 }
 
+// the value a predictive filter keeps for particle pi (ObsFinishArgs::vc_out): the vc that
+// obs_ll_value formed, or NaN where it returned early (a masked bank's blacked-out filter)
+__device__ __forceinline__ double obs_vc_kept(const ObsFinishArgs& a, long long pi, double vc) {
+  return a.ftab && a.ftab[3 * (pi / a.Pf)] == 0.0 ? __longlong_as_double(0x7ff8000000000000ll) : vc;
+}
+
 __global__ __launch_bounds__(kB) void k_obs_ll(ObsFinishArgs a) {
   const long long o = (long long)blockIdx.x * kB + threadIdx.x;
   unsigned long long key = 0;            // below ord_enc of any double
   if (o < a.n_out) {
     double vc;
     const double llv = obs_ll_value(a, o, vc);
-    a.ll[a.own ? a.own[a.ll_offset + o] : a.ll_offset + o] = llv;
+    const long long pi = a.own ? a.own[a.ll_offset + o] : a.ll_offset + o;
+    a.ll[pi] = llv;
+    if (a.vc_out) a.vc_out[pi] = obs_vc_kept(a, pi, vc);
     if (a.health) {
       count_event(a.health + kHealthObsVar, !(vc > 0.0));
       count_event(a.health + kHealthObsLL, !isfinite(llv));
@@ -1323,6 +1331,7 @@ __global__ __launch_bounds__(1024) void k_small_resample(NormArgs na, ResampleAr
     if (p < P) {
       llv = obs_ll_value(na.obs, g0 + p, vc);
       na.obs.ll[g0 + p] = llv;
+      if (na.obs.vc_out) na.obs.vc_out[g0 + p] = obs_vc_kept(na.obs, g0 + p, vc);
     }
     if (na.obs.health) {
       count_event(na.obs.health + kHealthObsVar, p < P && !(vc > 0.0));

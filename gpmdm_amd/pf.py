@@ -55,7 +55,7 @@ from __future__ import annotations
 import ctypes
 import os
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -109,6 +109,46 @@ class Smoothed:
     ancestors: Optional[torch.Tensor] = None            # (n, P) int64
     states: Optional[torch.Tensor] = None               # (n, P, d)
     classes: Optional[torch.Tensor] = None              # (n, P) int64
+
+
+class Innovation(NamedTuple):
+    """``GPMDM_PF.innovation``'s result (CPU tensors; a bank's carry a leading filter axis): how
+    surprising each joint of the frame just weighed was, against the propagated (pre-resample,
+    equally weighted) cloud.  With mu_pj the observation GP's mean at particle p, vc_p its
+    ``variance_common`` and il2_j = lambda_j^-2, over the particles with vc_p > 0 (``n_valid``):
+    ``gp_variance`` = il2_j mean_p vc_p, ``variance`` = ``spread`` + ``gp_variance``, ``residual`` =
+    z_j - ``mean``_j, ``zscore`` = residual / sqrt(variance), ``log_density`` = log mean_p N(z_j;
+    mu_pj, vc_p il2_j); the last three are NaN where ``observed`` is False."""
+    mean: torch.Tensor                                  # (D,)
+    spread: torch.Tensor                                # (D,)
+    gp_variance: torch.Tensor                           # (D,)
+    variance: torch.Tensor                              # (D,)
+    residual: torch.Tensor                              # (D,)
+    zscore: torch.Tensor                                # (D,)
+    log_density: torch.Tensor                           # (D,)
+    n_valid: torch.Tensor                               # () int64
+    observed: torch.Tensor                              # (D,) bool
+    states: Optional[torch.Tensor] = None               # (P, d)
+    variance_common: Optional[torch.Tensor] = None      # (P,)
+
+
+def _innovation_call(owner, entry, filters, particles):
+    """``innovation`` of a filter (``filters`` = ()) or a bank ((F_local,)): the library's
+    ``entry`` (its name; None for a bank without local filters) into host arrays with the leading
+    shape ``filters``, returned as an ``Innovation``."""
+    P, d, D = owner._num_particles, owner.latent_dim, owner.observation_dim
+    f7 = [np.full(filters + (D,), np.nan) for _ in range(7)]
+    nv = np.zeros(filters, dtype=np.int64)
+    ob = np.zeros(filters + (D,), dtype=np.uint8)
+    st = np.zeros(filters + (P, d)) if particles else None
+    vc = np.zeros(filters + (P,)) if particles else None
+    if entry is not None:
+        owner._sync_model()
+        out = _lib.InnovationOut(*[_lib.dptr(a) for a in f7], _lib.i64ptr(nv), ctypes.c_void_p(ob.ctypes.data),
+                                 _lib.dptr(st), _lib.dptr(vc))
+        _lib.check(getattr(_lib.load(), entry)(owner._h, ctypes.byref(out), owner._stream()), "innovation")
+    t = lambda a: None if a is None else torch.from_numpy(a)   # noqa: E731
+    return Innovation(*map(t, f7), torch.from_numpy(nv), torch.from_numpy(ob.astype(bool)), t(st), t(vc))
 
 
 def _check_smoothing_lag(L) -> int:
@@ -207,8 +247,9 @@ class GPMDM_PF:
                  rng: str = "torch", seed=None, resample: str = "multinomial", process_group=None,
                  shard=None, exchange=None, dedup: bool = True, shard_order: bool = True,
                  dyn_tiles: str = "auto", devices=None, obs_cutoff: bool = False, transport: str = "rccl",
-                 smoothing_lag: int = 0):
+                 smoothing_lag: int = 0, predictive: bool = False):
         self._smoothing_lag = _check_smoothing_lag(smoothing_lag)
+        self._predictive = bool(predictive)
         self._gpmdm = gpmdm
         self._gpmdm.set_evaluation_mode()
         self._markov_switching_model = torch.as_tensor(markov_switching_model).type(self.dtype)
@@ -286,6 +327,8 @@ class GPMDM_PF:
                 except Exception:
                     lib.gpmdm_pf_destroy(h)     # (a history above the memory limit: no handle is left behind)
                     raise
+            if self._predictive:
+                _lib.check(lib.gpmdm_pf_set_predictive(h, 1), "predictive")
             return h
 
         self._peers = []                        # devices=: ranks 1.. as (handle, device index)
@@ -629,12 +672,45 @@ class GPMDM_PF:
         _lib.check(_lib.load().gpmdm_pf_predict(self._h, _lib.dptr(out), self._stream()), "predict")
         return torch.from_numpy(out)
 
-    def current_observation(self, spread: bool = True):
+    def set_predictive(self, on: bool = True):
+        """Keep, from the next update on, each particle's GP predictive-variance factor
+        vc = 1 - k^T K_y^-1 k as the likelihood forms it (one 8-byte store per particle), for
+        ``innovation`` and ``current_observation(gp_variance=True)`` (gpmdm_pf_set_predictive; the
+        constructor's ``predictive``).  Off, an update issues exactly the work it issued without
+        the feature.  Either way the filter's results are bitwise the same.  Between updates only."""
+        self._sync_model()
+        lib = _lib.load()
+        for h in [self._h] + [p[0] for p in self._peers]:
+            _lib.check(lib.gpmdm_pf_set_predictive(h, 1 if on else 0), "set_predictive")
+        self._predictive = bool(on)
+
+    @property
+    def predictive(self) -> bool:
+        return self._predictive
+
+    def innovation(self, particles: bool = False) -> Innovation:
+        """Per-joint innovations of the frame the last ``update`` weighed (gpmdm_pf_innovation):
+        ``pf.update(z); inn = pf.innovation(); suspicious = inn.zscore.abs() > k``.  Evaluated on the
+        device from what the frame left there -- the propagated cloud, each particle's vc and the
+        staged ``z`` -- by the pose read-out's tile with a log-sum-exp epilogue; no state change,
+        no draw, the same frame gives bitwise the same result.  ``particles``: also the propagated
+        states and their vc (``states``, ``variance_common``).  Needs ``predictive``; ValueError
+        when it is off or the filter is sharded, RuntimeError before the first update after
+        ``reset`` / ``load_state`` / ``set_predictive``."""
+        if not self._predictive:
+            raise ValueError("innovation: build the filter with predictive=True or call set_predictive(True)")
+        return _innovation_call(self, "gpmdm_pf_innovation", (), particles)
+
+    def current_observation(self, spread: bool = True, gp_variance: bool = False):
         """The filtered pose: the observation GP's mean (gpmdm.py:955-957) averaged over the
         particles the filter holds now, ``mean[j] = (1/P) sum_p mu_j(x_p)`` -- the denoised
         joint angles, and after masked updates the imputed values of the joints that were not
         seen -- and with ``spread`` the cloud's variance of each, ``(1/P) sum_p (mu_j(x_p) -
-        mean[j])^2`` (the particles' disagreement, not the GP's own noise variance).  Computed
+        mean[j])^2`` (the particles' disagreement, not the GP's own noise variance).  With
+        ``gp_variance`` (a ``predictive`` filter, after an update) a last tensor is appended: the
+        GP's own predictive variance ``il2_j mean_s vc[ancestor(s)]`` of the resampled cloud
+        (gpmdm_pf_observation_gp; gathered from the values the frame's likelihood formed), so that
+        ``spread + gp_variance`` is the calibrated posterior pose variance.  Computed
         on the device by a mean-only GP tile (gpmdm_pf_observation); does not change the
         filter state and draws no random numbers; the same cloud gives bitwise the same
         values.  A sharded filter evaluates its replicated cloud on rank 0."""
@@ -644,9 +720,15 @@ class GPMDM_PF:
         var = np.zeros(D) if spread else None
         _lib.check(_lib.load().gpmdm_pf_observation(self._h, _lib.dptr(mean), _lib.dptr(var), self._stream()),
                    "current_observation")
-        if spread:
-            return torch.from_numpy(mean), torch.from_numpy(var)
-        return torch.from_numpy(mean)
+        res = (torch.from_numpy(mean), torch.from_numpy(var)) if spread else (torch.from_numpy(mean),)
+        if gp_variance:
+            if not self._predictive:
+                raise ValueError("gp_variance: build the filter with predictive=True or call set_predictive(True)")
+            gpv = np.zeros(D)
+            _lib.check(_lib.load().gpmdm_pf_observation_gp(self._h, _lib.dptr(gpv), self._stream()),
+                       "current_observation")
+            res = res + (torch.from_numpy(gpv),)
+        return res if len(res) > 1 else res[0]
 
     def current_observation_mean(self) -> torch.Tensor:
         """``current_observation``'s mean alone: the observation-space counterpart of

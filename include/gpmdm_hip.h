@@ -624,6 +624,60 @@ int gpmdm_bank_set_smoothing(gpmdm_pf_t pf, int lag);
 int gpmdm_bank_smoothed(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_smoothed_out* out,
                         void* stream);
 
+/* Per-joint innovations of the frame just weighed, and the GP's own predictive variance.
+ * gpmdm_pf_set_predictive(pf, 1): from then on every weigh keeps, per particle, the value
+ * vc = 1 - k^T K_y^-1 k its likelihood formed (one 8-byte store per particle; a blacked-out filter
+ * of a masked bank keeps NaN), and remembers the frame's staged observation and mask.  Off (the
+ * default), a frame issues exactly the launches and results it issued without the feature.
+ * Between frames only (GPMDM_E_STATE inside a step); a pending pre-switch stays pending.
+ * gpmdm_pf_innovation: with x~_p the propagated particles of that frame (pre-resample, equally
+ * weighted), mu_pj the observation GP's mean at x~_p, il2_j = lambda_j^-2, V = {p : vc_p > 0},
+ * n_valid = |V|, z the frame's observation and o its mask:
+ *   mean_j, spread_j   (1/P) sum_p mu_pj and (1/P) sum_p (mu_pj - mean_j)^2 -- bitwise what
+ *                      gpmdm_pf_observation gives on the cloud x~
+ *   gp_variance_j      il2_j (1/n_valid) sum_{p in V} vc_p
+ *   variance_j         spread_j + gp_variance_j (law of total variance of the mixture)
+ *   residual_j         z_j - mean_j                           (NaN where o_j is false)
+ *   zscore_j           residual_j / sqrt(variance_j)           (NaN where o_j is false)
+ *   log_density_j      log (1/n_valid) sum_{p in V} N(z_j; mu_pj, vc_p il2_j), a proper Gaussian
+ *                      with the float64 ln 2 pi               (NaN where o_j is false)
+ * Particles outside V are left out of every vc-dependent quantity; with n_valid = 0 -- also a
+ * frame or a bank's filter with no observed dimension, where no vc exists -- gp_variance,
+ * variance, zscore and log_density are NaN.  states / variance_common: x~_p and vc_p in particle
+ * order.  Every reduction has a fixed order: the same frame gives the same bits on every call.
+ * Allowed between frames and between gpmdm_pf_propagate / gpmdm_pf_weigh and gpmdm_pf_resample
+ * (a deferred likelihood finish is run first; the frame's results do not change).
+ * GPMDM_E_INVALID: the feature is off, or the filter is sharded (only ll is exchanged).
+ * GPMDM_E_STATE: no frame weighed since the feature was switched on or since gpmdm_pf_propagate,
+ * gpmdm_pf_init, gpmdm_pf_import or gpmdm_pf_set_model.
+ * gpmdm_pf_observation_gp: the posterior counterpart, gp_var_j = il2_j (1/n_valid) sum_{s: vc > 0}
+ * vc[ridx[s]] over the resampled cloud's ancestors (gathered, never recomputed): spread (of
+ * gpmdm_pf_observation) + gp_var is the calibrated posterior pose variance.  Needs a completed
+ * resample of a frame weighed with the feature on (GPMDM_E_STATE otherwise).
+ * The gpmdm_pf_* calls refuse banks (GPMDM_E_INVALID); the gpmdm_bank_* calls serve any handle,
+ * outputs filter-major.  Each call queues everything on `stream`, ends with one pinned copy and
+ * one wait, and is covered by the handle's lifecycle waits.  With `out` (`gp_var`) NULL the
+ * kernels are launched only (timing), as gpmdm_pf_observation does it. */
+typedef struct gpmdm_innovation_out {   /* host arrays; any may be NULL; F = 1 for a single filter */
+  double*  mean;              /* F x D */
+  double*  spread;            /* F x D */
+  double*  gp_variance;       /* F x D */
+  double*  variance;          /* F x D */
+  double*  residual;          /* F x D */
+  double*  zscore;            /* F x D */
+  double*  log_density;       /* F x D */
+  int64_t* n_valid;           /* F */
+  uint8_t* observed;          /* F x D: the mask the frame was weighed with */
+  double*  states;            /* F x P x d */
+  double*  variance_common;   /* F x P */
+} gpmdm_innovation_out;
+int gpmdm_pf_set_predictive(gpmdm_pf_t pf, int on);
+int gpmdm_pf_innovation(gpmdm_pf_t pf, const gpmdm_innovation_out* out, void* stream);
+int gpmdm_pf_observation_gp(gpmdm_pf_t pf, double* gp_var /* D */, void* stream);
+int gpmdm_bank_set_predictive(gpmdm_pf_t pf, int on);
+int gpmdm_bank_innovation(gpmdm_pf_t pf, const gpmdm_innovation_out* out, void* stream);
+int gpmdm_bank_observation_gp(gpmdm_pf_t pf, double* gp_var /* F x D */, void* stream);
+
 /* Device-side GP factor: the recipe of _precompute_kernel_inverses
  * (gpmdm.py:1284-1305) for one GP block -- the observation GP, or one class block of the
  * dynamics GP (the reference's full masked matrix has exact zeros off the class blocks):
