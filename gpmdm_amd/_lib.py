@@ -70,6 +70,12 @@ class InnovationOut(ctypes.Structure):
                 ("states", _dp), ("variance_common", _dp)]
 
 
+class GateOut(ctypes.Structure):
+    """gpmdm_gate_out: host arrays, any may be NULL."""
+    _fields_ = [("zscore", _dp), ("exceeded", c_void_p), ("gated", c_void_p), ("used", c_void_p),
+                ("n_gated", _i64p), ("n_valid", _i64p), ("overflow", POINTER(c_int32))]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "gpmdm_model_create": (c_int, [POINTER(ModelDesc), c_int, POINTER(c_void_p)]),
@@ -135,6 +141,8 @@ _SIGS = {
     "gpmdm_bank_set_predictive": (c_int, [c_void_p, c_int]),
     "gpmdm_bank_innovation": (c_int, [c_void_p, POINTER(InnovationOut), c_void_p]),
     "gpmdm_bank_observation_gp": (c_int, [c_void_p, _dp, c_void_p]),
+    "gpmdm_pf_set_gate": (c_int, [c_void_p, c_double, c_double]),
+    "gpmdm_pf_gate_report": (c_int, [c_void_p, POINTER(GateOut), c_void_p]),
     "gpmdm_pf_set_comm": (c_int, [c_void_p, c_void_p, c_int]),
     "gpmdm_comm_unique_id": (c_int, [c_void_p]),
     "gpmdm_comm_init": (c_int, [c_int, c_int, c_void_p, c_int, POINTER(c_void_p)]),

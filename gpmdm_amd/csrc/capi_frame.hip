@@ -602,6 +602,10 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
     pf->pv_has_vc = !(masked && pf->D_obs == 0) && nl > 0;
     pf->pv_weighed = true;
     pf->pv_resampled = false;
+    // gating (capi_gate.hip): the decision from this frame's own innovations and, where it
+    // rejects joints, ll and the block maxima of the kept ones -- behind the finish, before the
+    // normaliser; off, nothing is launched
+    if (pf->gate_k > 0.0 && pf->F == 1) TRY(gate_frame(pf, s));
   }
   pf->propagated = true;
   pf->dyn_done = false;

@@ -19,6 +19,7 @@ int iv_wait(gpmdm_pf* pf) {
 
 static int set_predictive(gpmdm_pf* pf, int on) {
   if (pf->mid_step()) return fail(GPMDM_E_STATE, "set_predictive between switch and resample");
+  if (!on && pf->gate_k > 0.0) return fail(GPMDM_E_STATE, "set_predictive(0) while the gate is on (gpmdm_pf_set_gate)");
   gpmdm_model* m = pf->m;
   HIPCHK(hipSetDevice(m->device));
   // the last frame's finish may still write vc_prop: it precedes the frame's read-out (a

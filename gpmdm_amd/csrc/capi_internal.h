@@ -11,6 +11,7 @@
 //                      gpmdm_bank_smoothed)
 //   capi_innov.hip     per-joint innovations and the GP's predictive variance (gpmdm_pf_set_predictive,
 //                      gpmdm_pf_innovation, gpmdm_pf_observation_gp and the banks')
+//   capi_gate.hip      outlier gating inside the frame (gpmdm_pf_set_gate, gpmdm_pf_gate_report)
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -394,7 +395,21 @@ struct gpmdm_pf {
   size_t iv_part_cap = 0, iv_out_cap = 0;
   hipEvent_t iv_ev = nullptr;
   bool iv_pending = false;
-  void pv_clear() { pv_weighed = pv_has_vc = pv_resampled = false; }
+  void pv_clear() { pv_weighed = pv_has_vc = pv_resampled = gt_ready = false; }
+  // Outlier gating inside the frame (gpmdm_pf_set_gate, gpmdm_pf_gate_report; obs_gate.h,
+  // capi_gate.hip).  gate_k > 0: on (single filters on one rank, predictive on): weigh ends with
+  // gate_frame -- the innovation launches into scratch of the gate's own (gt_part, gt_out), then
+  // the decision, the re-weigh tile and its finish -- on the frame's stream, so the frame's
+  // read-out follows them and the lifecycle waits cover them.  gt_tab: the device table
+  // (GateTab), gt_sp the re-weigh partials, gt_lil the host's log il2_j of the filter's model
+  // (uploaded by set_gate and again by a rebind), gt_pin the report's pinned landing buffer.
+  // gt_ready: a frame has been weighed in gated mode since the last propagate, init, import,
+  // rebind, set_predictive or set_gate (gt_host: a blackout frame, no launch; the report is the
+  // host's).
+  double gate_k = 0.0, gate_limit = 0.5;
+  bool gt_ready = false, gt_host = false;
+  double *gt_part = nullptr, *gt_out = nullptr, *gt_tab = nullptr, *gt_sp = nullptr, *gt_lil = nullptr, *gt_pin = nullptr;
+  size_t gt_part_cap = 0, gt_sp_cap = 0;
   // likelihood finish deferred into the resampling launch (single-shard small filters:
   // k_small_resample computes ll first, one launch less per frame); flush_ll runs it for
   // any reader of ll that comes first
@@ -739,6 +754,9 @@ struct gpmdm_pf {
     hfree(iv_pin);
     hfree(pv_mask);
     if (iv_ev) (void)hipEventDestroy(iv_ev);
+    double* gd[] = {gt_part, gt_out, gt_tab, gt_sp, gt_lil};
+    for (double* p : gd) dfree(p);
+    hfree(gt_pin);
     dfree(bmax);
     dfree(bmax_rows);
     dfree(owner);
@@ -822,6 +840,10 @@ struct FcTables {
 ReadoutParams rollout_readout(const gpmdm_pf* pf, const double* X, double* part, double* out);
 int sm_set(gpmdm_pf* pf, int lag);     // (set_smoothing of a checked handle, single or bank)
 int iv_wait(gpmdm_pf* pf);             // an innovation call's launches in flight (capi_innov.hip)
+// gating (capi_gate.hip): the end of a gated-mode weigh on s; the log il2 table of the filter's
+// (new) model
+int gate_frame(gpmdm_pf* pf, hipStream_t s);
+int gate_rebind(gpmdm_pf* pf);
 // staging of a forecast's per-step clouds may take this much device memory (H x P x (d + 1)
 // doubles); so may the smoothing ring, and a smoothed read-out's staging of the particle rows
 constexpr size_t kForecastStageBytes = (size_t)1 << 30;

@@ -680,6 +680,7 @@ int gpmdm_pf_set_model(gpmdm_pf_t pf, gpmdm_model_t m) {
     TRY(install_obs_mask(pf, mask));
   }
   pf->pv_clear();                      // the kept vc was the old model's
+  TRY(gate_rebind(pf));                // the gate's log il2 table is the new model's
   return sm_clear(pf, ls);             // smoothing: older frames were the old model's
 }
 

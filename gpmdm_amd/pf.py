@@ -151,6 +151,35 @@ def _innovation_call(owner, entry, filters, particles):
     return Innovation(*map(t, f7), torch.from_numpy(nv), torch.from_numpy(ob.astype(bool)), t(st), t(vc))
 
 
+class GateReport(NamedTuple):
+    """``GPMDM_PF.gate_report``'s result (CPU tensors and Python scalars): what the gate decided
+    for the frame the last ``update`` weighed.  ``zscore`` is bitwise ``innovation().zscore`` of
+    that frame (NaN where unobserved); ``exceeded`` = observed and |zscore| > ``threshold``;
+    ``gated`` = ``exceeded`` when between 1 and floor(limit D_obs) joints exceeded, else empty
+    (``overflow``: more did, and the frame was weighed as observed); ``used`` = observed and not
+    ``gated``, the joints the frame's weights rest on."""
+    threshold: float
+    zscore: torch.Tensor                                # (D,)
+    exceeded: torch.Tensor                              # (D,) bool
+    gated: torch.Tensor                                 # (D,) bool
+    used: torch.Tensor                                  # (D,) bool
+    n_gated: int
+    n_valid: int
+    overflow: bool
+
+
+def _check_gate(k, limit):
+    """``gate`` (None: off) and ``gate_limit`` as floats; raised here, before the library is touched."""
+    real = lambda x: not isinstance(x, bool) and isinstance(x, (int, float, np.integer, np.floating))   # noqa: E731
+    if not real(limit) or not 0.0 < float(limit) <= 1.0:
+        raise ValueError(f"gate_limit must be a real number in (0, 1], got {limit!r}")
+    if k is None:
+        return None, float(limit)
+    if not real(k) or not 0.0 < float(k) < float("inf"):
+        raise ValueError(f"gate must be None or a finite real number > 0, got {k!r}")
+    return float(k), float(limit)
+
+
 def _check_smoothing_lag(L) -> int:
     if isinstance(L, bool) or not isinstance(L, (int, np.integer)):
         raise ValueError(f"smoothing lag must be an integer, got {L!r}")
@@ -247,9 +276,12 @@ class GPMDM_PF:
                  rng: str = "torch", seed=None, resample: str = "multinomial", process_group=None,
                  shard=None, exchange=None, dedup: bool = True, shard_order: bool = True,
                  dyn_tiles: str = "auto", devices=None, obs_cutoff: bool = False, transport: str = "rccl",
-                 smoothing_lag: int = 0, predictive: bool = False):
+                 smoothing_lag: int = 0, predictive: bool = False, gate=None, gate_limit: float = 0.5):
         self._smoothing_lag = _check_smoothing_lag(smoothing_lag)
-        self._predictive = bool(predictive)
+        self._gate, self._gate_limit = _check_gate(gate, gate_limit)
+        if self._gate is not None and (process_group is not None or shard is not None):
+            raise ValueError("gate= serves single filters on one rank: no process_group or shard")
+        self._predictive = bool(predictive) or self._gate is not None   # (the gate reads the frame's vc)
         self._gpmdm = gpmdm
         self._gpmdm.set_evaluation_mode()
         self._markov_switching_model = torch.as_tensor(markov_switching_model).type(self.dtype)
@@ -285,7 +317,9 @@ class GPMDM_PF:
                 raise ValueError("shard= with rng='philox' needs an explicit seed (identical on every rank)")
         else:
             self._world, self._rank = 1, 0
-        self._collective = process_group is not None and self._world > 1
+        if self._gate is not None and self._world > 1:
+            raise ValueError("gate= serves single filters on one rank, not sharded filters")
+        self._collective =process_group is not None and self._world > 1
         if self._collective and rng == "torch":
             from .distributed import identical_on_all_ranks
             if not identical_on_all_ranks(torch.get_rng_state().numpy().tobytes(), process_group, self.device):
@@ -329,6 +363,8 @@ class GPMDM_PF:
                     raise
             if self._predictive:
                 _lib.check(lib.gpmdm_pf_set_predictive(h, 1), "predictive")
+            if self._gate is not None:
+                _lib.check(lib.gpmdm_pf_set_gate(h, self._gate, self._gate_limit), "gate")
             return h
 
         self._peers = []                        # devices=: ranks 1.. as (handle, device index)
@@ -677,7 +713,10 @@ class GPMDM_PF:
         vc = 1 - k^T K_y^-1 k as the likelihood forms it (one 8-byte store per particle), for
         ``innovation`` and ``current_observation(gp_variance=True)`` (gpmdm_pf_set_predictive; the
         constructor's ``predictive``).  Off, an update issues exactly the work it issued without
-        the feature.  Either way the filter's results are bitwise the same.  Between updates only."""
+        the feature.  Either way the filter's results are bitwise the same.  Between updates only;
+        ValueError for ``set_predictive(False)`` while the gate is on."""
+        if not on and getattr(self, "_gate", None) is not None:
+            raise ValueError("set_predictive(False) while the gate is on: call set_gate(None) first")
         self._sync_model()
         lib = _lib.load()
         for h in [self._h] + [p[0] for p in self._peers]:
@@ -700,6 +739,62 @@ class GPMDM_PF:
         if not self._predictive:
             raise ValueError("innovation: build the filter with predictive=True or call set_predictive(True)")
         return _innovation_call(self, "gpmdm_pf_innovation", (), particles)
+
+    def set_gate(self, gate=None, limit: float = 0.5):
+        """Reject outlier joints inside ``update``, from the next update on (gpmdm_pf_set_gate; the
+        constructor's ``gate`` / ``gate_limit``): ``pf = GPMDM_PF(m, T, P, gate=6.0); pf.update(z);
+        pf.gate_report().gated``.  With the frame's own innovation z-scores (``innovation``'s, on
+        the propagated cloud), joints that are observed and have |zscore| > ``gate`` are dropped
+        from the frame's likelihood before the particles are normalised and resampled, provided at
+        most floor(``limit`` x observed joints) exceed; if more do, nothing is dropped (a surprise
+        shared by most of the body is a lost track, not a marker fault).  Everything runs on the
+        device behind the likelihood finish, without a host wait: the innovation tile
+        (k_obs_innov), the decision (k_gate_decide) and, effective only where something is
+        rejected, a mean-only re-weigh (k_obs_reweigh, k_gate_finish) with each particle's stored
+        vc -- no second N x N pass.  No draw from any generator; a frame that rejects nothing is
+        bitwise the frame of the same filter with ``predictive=True`` and no gate; the same frame
+        gives the same bits.  ``innovation()`` keeps reporting against the caller's mask, and
+        ``current_observation()`` imputes rejected joints as it imputes unobserved ones.
+        ``gate=None`` turns it off: an update then issues exactly the work it issued without the
+        feature.  Needs ``predictive`` (ValueError otherwise); single filters on one rank; between
+        updates only.  Invalidates the last report."""
+        k, lim = _check_gate(gate, limit)
+        if k is not None and self._world > 1:
+            raise ValueError("gate serves single filters on one rank, not sharded filters")
+        if k is not None and not self._predictive:
+            raise ValueError("gate: build the filter with predictive=True or call set_predictive(True)")
+        self._sync_model()
+        _lib.check(_lib.load().gpmdm_pf_set_gate(self._h, 0.0 if k is None else k, lim), "set_gate")
+        self._gate, self._gate_limit = k, lim
+
+    @property
+    def gate(self):
+        """The gate's z-score threshold, or None when it is off."""
+        return self._gate
+
+    @property
+    def gate_limit(self) -> float:
+        return self._gate_limit
+
+    def gate_report(self) -> GateReport:
+        """What the gate decided for the frame the last ``update`` weighed (gpmdm_pf_gate_report:
+        one copy of k_gate_decide's device table and one wait): ``gated`` are the joints the frame
+        rejected, ``used`` the ones its weights rest on, ``zscore`` bitwise ``innovation().zscore``.
+        No state change, no draw.  ValueError with the gate off, RuntimeError before the first
+        update after ``reset`` / ``load_state`` / ``set_predictive`` / ``set_gate``."""
+        if getattr(self, "_gate", None) is None:
+            raise ValueError("gate_report: build the filter with gate=k or call set_gate(k)")
+        D = self.observation_dim
+        zs = np.full(D, np.nan)
+        ex, ga, us = (np.zeros(D, dtype=np.uint8) for _ in range(3))
+        ng, nv, ov = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64), ctypes.c_int32(0)
+        self._sync_model()
+        out = _lib.GateOut(_lib.dptr(zs), *[ctypes.c_void_p(a.ctypes.data) for a in (ex, ga, us)],
+                           _lib.i64ptr(ng), _lib.i64ptr(nv), ctypes.pointer(ov))
+        _lib.check(_lib.load().gpmdm_pf_gate_report(self._h, ctypes.byref(out), self._stream()), "gate_report")
+        b = lambda a: torch.from_numpy(a.astype(bool))   # noqa: E731
+        return GateReport(self._gate, torch.from_numpy(zs), b(ex), b(ga), b(us), int(ng[0]), int(nv[0]),
+                          bool(ov.value))
 
     def current_observation(self, spread: bool = True, gp_variance: bool = False):
         """The filtered pose: the observation GP's mean (gpmdm.py:955-957) averaged over the

@@ -678,6 +678,49 @@ int gpmdm_bank_set_predictive(gpmdm_pf_t pf, int on);
 int gpmdm_bank_innovation(gpmdm_pf_t pf, const gpmdm_innovation_out* out, void* stream);
 int gpmdm_bank_observation_gp(gpmdm_pf_t pf, double* gp_var /* F x D */, void* stream);
 
+/* Outlier gating inside the frame: joints whose innovation z-score is too large are dropped from
+ * the frame's likelihood before the particles are normalised and resampled.
+ * gpmdm_pf_set_gate(pf, threshold, limit): threshold k > 0 switches it on (threshold <= 0: off),
+ * 0 < limit <= 1.  From then on every weigh of a frame with an observed dimension ends, on the
+ * frame's stream and without a host wait, with the innovation launches of gpmdm_pf_innovation
+ * (into scratch of the gate's own) and, with o the frame's mask and zscore_j exactly what
+ * gpmdm_pf_innovation reports for the frame,
+ *   exceeded_j = o_j and |zscore_j| > k                  (false for NaN)
+ *   cap        = floor(limit D_obs)                      (host, fp64)
+ *   gated      = exceeded if 1 <= n_exceeded <= cap; empty, with overflow set, if n_exceeded > cap
+ *                (a surprise shared by most of the body is no marker fault: weighed as observed)
+ *   used       = o and not gated, D' = |used|.
+ * When something is gated every particle's log-likelihood is replaced, before the normaliser, by
+ * the masked frame's value on the kept joints,
+ *   ll'_p = -1/2 S'_p / vc_p - D' log vc_p - sum_{j in used} log il2_j - (D'/2 ln 2 pi)_f32,
+ *   S'_p = sum_{j in used} (z_j - mu_pj)^2 lambda_j^2,
+ * with the stored vc_p (the N x N pass is not run again; vc_p <= 0 gives NaN as before; D' = 0
+ * gives exactly 0).  When nothing is gated the frame is bitwise the frame without the gate.  The
+ * health counters and the cutoff's counters are those of the first finish; gpmdm_pf_innovation
+ * keeps reporting against the caller's mask.  Off (the default), a frame issues exactly the
+ * launches it issued without the feature.
+ * Between frames only (GPMDM_E_STATE inside a step), and only with the predictive switch on
+ * (GPMDM_E_STATE; gpmdm_pf_set_predictive(pf, 0) is refused while the gate is on).
+ * GPMDM_E_INVALID: a bank, a sharded filter, a threshold that is NaN or infinite, a limit outside
+ * (0, 1].  The call invalidates the last report.
+ * gpmdm_pf_gate_report: what the last gated-mode frame decided -- one copy and one wait on
+ * `stream`.  Allowed between gpmdm_pf_propagate / gpmdm_pf_weigh and gpmdm_pf_resample and after
+ * the resample.  A blackout frame reports nothing exceeded, nothing used and n_valid = 0.
+ * GPMDM_E_INVALID: the gate is off.  GPMDM_E_STATE: no frame weighed in gated mode since
+ * gpmdm_pf_init, gpmdm_pf_import, gpmdm_pf_set_model, gpmdm_pf_set_predictive or
+ * gpmdm_pf_set_gate. */
+typedef struct gpmdm_gate_out {   /* host arrays; any may be NULL */
+  double*  zscore;     /* D: the frame's, NaN where unobserved */
+  uint8_t* exceeded;   /* D */
+  uint8_t* gated;      /* D */
+  uint8_t* used;       /* D: the joints the frame's weights rest on */
+  int64_t* n_gated;    /* 1 */
+  int64_t* n_valid;    /* 1 */
+  int32_t* overflow;   /* 1 */
+} gpmdm_gate_out;
+int gpmdm_pf_set_gate(gpmdm_pf_t pf, double threshold, double limit);   /* threshold <= 0: off */
+int gpmdm_pf_gate_report(gpmdm_pf_t pf, const gpmdm_gate_out* out, void* stream);
+
 /* Device-side GP factor: the recipe of _precompute_kernel_inverses
  * (gpmdm.py:1284-1305) for one GP block -- the observation GP, or one class block of the
  * dynamics GP (the reference's full masked matrix has exact zeros off the class blocks):
