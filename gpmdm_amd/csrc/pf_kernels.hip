@@ -911,6 +911,17 @@ __global__ __launch_bounds__(1024) void k_norm_total(NormArgs a) {
 // (k_guide, k_sys_marks, k_resample) instead of stored by a CDF pass: the same expression on
 // the same operands, so every value -- and every index -- is the stored CDF's, one dependent
 // launch fewer per frame.
+//
+// Not monotone to the last ulp for general weights: boff[b] (a Hillis-Steele prefix) and
+// boff[b-1] + local[last of b-1] are two associations of one sum, the lanes of a wave scan add
+// in different orders, and a value before the last can exceed the forced 1.  The dips are a few
+// ulps (a host model of this summation order: tests/resample_ref.py, device_association_cdf),
+// far inside the (P + 8) 2^-53 band that any order of summing P non-negative terms has, so a
+// search that meets one still returns an ancestor whose exact CDF interval holds u to rounding.
+// tests/test_gpu_resample_edges.py holds every search form to that band, and to ancestors that
+// do not decrease with u, with uniforms placed on the CDF's values at every block boundary;
+// with weights in {0, 1} every sum is an integer, the CDF is monotone and the ancestors are
+// np.searchsorted's exactly.
 struct CdfView {
   const double* boff;
   const double* local;
@@ -934,8 +945,10 @@ __device__ __forceinline__ CdfView cdf_view(const ResampleArgs& a, long long f) 
 // last query: lanes 0-31 and 32-63 find those two by 32-way searches (32 independent probes
 // per step: four steps span 10^6 particles, against 20 dependent loads of a binary search),
 // then each lane searches the usually short range between them -- in registers when it holds
-// at most 64 particles (a collapsed cloud's range is often a single particle).  For a monotone
-// CDF every form returns the binary search's answer.
+// at most 64 particles (a collapsed cloud's range is often a single particle).  On a monotone
+// CDF every form returns the binary search's answer.  The evaluated CDF can dip by a few ulps
+// (see CdfView); across such a dip the forms may settle on different particles of the dip, each
+// inside the band its uniform allows -- the guarantee is the band, not one index.
 __global__ __launch_bounds__(kB) void k_guide(ResampleArgs a) {
   const long long f = blockIdx.y;
   const int lane = threadIdx.x & 63;
