@@ -254,22 +254,22 @@ static int gather_copy_down(gpmdm_pf* pf, double* recv, const double* stage, int
 static int exch_states(gpmdm_pf* pf, const double* normals, hipStream_t s) {
   TRY(propagate_dynamics(pf, normals, s));
   TRY(pack_part(pf, pf->xs_send, GPMDM_PACK_STATES, s));
-  HIPCHK(hipEventRecord(pf->cev[0], s));
-  HIPCHK(hipStreamWaitEvent(pf->cstream, pf->cev[0], 0));
+  HIPCHK(pf->cev[0].record(s));
+  HIPCHK(pf->cev[0].block(pf->cstream));
   return GPMDM_OK;
 }
 
 static int exch_ll(gpmdm_pf* pf, const double* zh, hipStream_t s) {
   TRY(weigh(pf, zh, s));
   TRY(pack_part(pf, pf->xl_send, GPMDM_PACK_LL, s));
-  HIPCHK(hipEventRecord(pf->cev[1], s));
-  HIPCHK(hipStreamWaitEvent(pf->cstream, pf->cev[1], 0));
+  HIPCHK(pf->cev[1].record(s));
+  HIPCHK(pf->cev[1].block(pf->cstream));
   return GPMDM_OK;
 }
 
 static int exch_finish(gpmdm_pf* pf, hipStream_t s) {
-  HIPCHK(hipEventRecord(pf->cev[2], pf->cstream));
-  HIPCHK(hipStreamWaitEvent(s, pf->cev[2], 0));
+  HIPCHK(pf->cev[2].record(pf->cstream));
+  HIPCHK(pf->cev[2].block(s));
   TRY(unpack_part(pf, pf->xs_recv, GPMDM_PACK_STATES, s));
   TRY(unpack_part(pf, pf->xl_recv, GPMDM_PACK_LL, s));
   return GPMDM_OK;
@@ -358,7 +358,7 @@ static bool rows_in_place(gpmdm_pf* pf) {
 }
 
 static int unpack_part(gpmdm_pf* pf, const double* recv, int part, hipStream_t s) {
-  const int* inv = pf->own_valid ? pf->own_inv : nullptr;
+  const int* inv = pf->own_valid ? pf->own_inv.p : nullptr;
   if (!rows_in_place(pf)) return launch_unpack_rows(pf, recv, part, inv, s);
   const int d = pf->m->d;
   const int w = part == GPMDM_PACK_ALL ? d + 2 : (part == GPMDM_PACK_STATES ? d + 1 : 1);
@@ -465,20 +465,16 @@ int gpmdm_pf_set_comm(gpmdm_pf_t pf, void* rccl_comm, int flags) {
   const long long rows = pf->pad * pf->n_ranks;
   int rc = 0;
   auto fail_out = [&](int code) { pf->release_comm(); return code; };
-  if ((rc = dalloc(&pf->xs_send, (size_t)pf->pad * (d + 1))) || (rc = dalloc(&pf->xl_send, (size_t)pf->pad)) ||
-      (rc = dalloc(&pf->xs_recv, (size_t)pf->P * (d + 1))) || (rc = dalloc(&pf->xl_recv, (size_t)pf->P)))
+  if ((rc = pf->xs_send.alloc((size_t)pf->pad * (d + 1))) || (rc = pf->xl_send.alloc((size_t)pf->pad)) ||
+      (rc = pf->xs_recv.alloc((size_t)pf->P * (d + 1))) || (rc = pf->xl_recv.alloc((size_t)pf->P)))
     return fail_out(rc);
-  if (pf->padded &&
-      ((rc = dalloc(&pf->xs_stage, (size_t)rows * (d + 1))) || (rc = dalloc(&pf->xl_stage, (size_t)rows))))
+  if (pf->padded && ((rc = pf->xs_stage.alloc((size_t)rows * (d + 1))) || (rc = pf->xl_stage.alloc((size_t)rows))))
     return fail_out(rc);
   // padding rows of the send buffers travel but are dropped: keep them defined
   if (hipMemset(pf->xs_send, 0, sizeof(double) * pf->pad * (d + 1)) != hipSuccess ||
       hipMemset(pf->xl_send, 0, sizeof(double) * pf->pad) != hipSuccess ||
       hipStreamCreateWithFlags(&pf->cstream, hipStreamNonBlocking) != hipSuccess)
     return fail_out(fail(GPMDM_E_HIP, "communicator stream / buffers"));
-  for (auto& ev : pf->cev)
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
-      return fail_out(fail(GPMDM_E_HIP, "communicator events"));
   pf->comm = comm;
   pf->comm_loop = lc != nullptr;
   return GPMDM_OK;

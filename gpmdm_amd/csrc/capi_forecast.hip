@@ -14,129 +14,39 @@ namespace gpmdm::capi {
 // Scratch of both entry points, and H x F result rows: {class_prob[C], state_mean[d]} of every
 // (step, filter), then {mean[D], spread[D]} of every (step, filter) -- the read-out writes the
 // F filters of a step as one contiguous block.
-static int ensure_scratch(gpmdm_pf* pf, int H, bool obs, bool per_filter_sums) {
+static int ensure_scratch(gpmdm_pf* pf, int H, bool obs, bool per_filter_sums, hipStream_t s) {
   const gpmdm_model* m = pf->m;
   const int C = m->C, d = m->d, D = m->D, F = pf->F;
   const long long P = pf->P;
   const long long nb = cdiv(P, 256), nbf = cdiv(pf->Pf, 256);
-#define NEED(ptr, n) do { if (!(ptr)) TRY(dalloc(&(ptr), (size_t)(n))); } while (0)
+#define NEED(buf, n) TRY(pf->buf.grow((size_t)(n), s))
   for (int k = 0; k < 2; ++k) {
-    NEED(pf->fc_X[k], P * d);
-    NEED(pf->fc_cls[k], P);
+    NEED(fc_X[k], P * d);
+    NEED(fc_cls[k], P);
   }
-  NEED(pf->fc_perm, P);
-  NEED(pf->fc_blockcounts, nb * C);
-  NEED(pf->fc_blockoff, nb * C);
-  NEED(pf->fc_mu, P * d);
-  NEED(pf->fc_part, F * nbf * d);
-  if (per_filter_sums) NEED(pf->fc_bcounts, F * nbf * C);
-  NEED(pf->fc_tab, 256);
+  NEED(fc_perm, P);
+  NEED(fc_blockcounts, nb * C);
+  NEED(fc_blockoff, nb * C);
+  NEED(fc_mu, P * d);
+  NEED(fc_part, F * nbf * d);
+  if (per_filter_sums) NEED(fc_bcounts, F * nbf * C);
+  NEED(fc_tab, 256);
+  NEED(fc_q, (size_t)pf->nparts_dyn_max * P);
+  if (obs) NEED(fc_ro_part, readout_part_doubles(pf->Pf, D, F));
 #undef NEED
-  const size_t qn = (size_t)pf->nparts_dyn_max * P;
-  if (pf->fc_q_cap < qn) {
-    dfree(pf->fc_q);
-    pf->fc_q_cap = 0;
-    TRY(dalloc(&pf->fc_q, qn));
-    pf->fc_q_cap = qn;
-  }
-  if (obs && !pf->fc_ro_part) TRY(dalloc(&pf->fc_ro_part, readout_part_doubles(pf->Pf, D, F)));
-  const size_t on = (size_t)H * F * (C + d + 2 * D);
-  if (pf->fc_out_cap < on) {
-    dfree(pf->fc_out);
-    hfree(pf->fc_pin);
-    pf->fc_out_cap = 0;
-    TRY(dalloc(&pf->fc_out, on));
-    TRY(halloc(&pf->fc_pin, on, 0));
-    pf->fc_out_cap = on;
-  }
-  if (!pf->fc_ev) HIPCHK(hipEventCreateWithFlags(&pf->fc_ev, hipEventDisableTiming));
-  return GPMDM_OK;
-}
-
-ReadoutParams rollout_readout(const gpmdm_pf* pf, const double* X, double* part, double* out) {
-  const gpmdm_model* m = pf->m;
-  ReadoutParams rp{};
-  rp.X = X;
-  rp.P = pf->Pf;
-  rp.F = pf->F;
-  rp.d = m->d;
-  rp.D = m->D;
-  rp.ls = m->y_ls_dev;
-  rp.Xrec = m->obs.Xrec;
-  rp.nks = ksteps((int)m->N);
-  rp.Bro = m->ro_beta;
-  rp.n_groups = readout_groups(m->D);
-  rp.part = part;
-  rp.out = out;
-  return rp;
+  return pf->fc_out.reserve((size_t)H * F * (C + d + 2 * D), s);
 }
 
 // The filter's grouping passes on the forecast's own tables: classes `cls` (all pf->P particles,
 // a bank's F x Pf among them), whose per-block counts are in fc_blockcounts.
 static void fc_group(gpmdm_pf* pf, const int* cls, hipStream_t s) {
   const gpmdm_model* m = pf->m;
-  const long long P = pf->P;
-  const FcTables tb{pf->fc_tab};
   ScanArgs sc{};
-  sc.nb = (int)cdiv(P, 256);
-  sc.C = m->C;
-  sc.pt = m->dyn_set(true)[0].geo.pt();
-  sc.lo = 0;
-  sc.hi = P;
-  sc.blockcounts = pf->fc_blockcounts;
-  sc.cls_new = cls;
-  sc.blockoff = pf->fc_blockoff;
-  sc.class_start = tb.class_start();
-  sc.counts = tb.counts();
-  sc.seg_pos_begin = tb.seg_begin();
-  sc.seg_pos_end = tb.seg_end();
-  sc.seg_out_base = tb.seg_out();
-  sc.seg_tile_start = tb.seg_tiles();
-  launch_scan_counts(sc, s);
   GroupArgs ga{};
-  ga.P = P;
-  ga.n = P;
-  ga.C = m->C;
-  ga.cls_new = cls;
-  ga.class_start = tb.class_start();
-  ga.blockoff = pf->fc_blockoff;
-  ga.perm = pf->fc_perm;
+  fill_grouping(sc, ga, ClassTables{pf->fc_tab}, pf->fc_blockcounts, pf->fc_blockoff, pf->fc_perm, cls, pf->P, m->C,
+                m->dyn_set(true)[0].geo.pt());
+  launch_scan_counts(sc, s);
   launch_group(ga, s);
-}
-
-// Each class's dynamics GP on the scratch cloud X, rows in the grouped order of fc_group
-// (gpmdm_pf_predict's launches: every particle is evaluated), into fc_q / fc_mu.
-static void fc_tiles(gpmdm_pf* pf, const double* X, hipStream_t s) {
-  gpmdm_model* m = pf->m;
-  const int C = m->C, d = m->d;
-  const long long P = pf->P;
-  const std::vector<GpImage>& dset = m->dyn_set(true);
-  const FcTables tb{pf->fc_tab};
-  for (int c0 = 0; c0 < C; c0 += kMaxSeg) {
-    const int ns = std::min(kMaxSeg, C - c0);
-    TileParams tp{};
-    int njm = 0;
-    for (int k = 0; k < ns; ++k) {
-      tp.seg[k] = dset[c0 + k].seg();
-      njm = std::max(njm, dset[c0 + k].n_j);
-    }
-    tp.n_seg = ns;
-    tp.geo = dset[c0].geo;
-    tp.tiles_ub = (int)(cdiv(P, tp.geo.pt()) + ns);
-    tp.n_j_max = njm;
-    tp.seg_pos_begin = tb.seg_begin() + c0;
-    tp.seg_pos_end = tb.seg_end() + c0;
-    tp.seg_out_base = tb.seg_out() + c0;
-    tp.seg_tile_start = tb.seg_tiles() + c0;
-    tp.perm = pf->fc_perm;
-    tp.X = X;
-    fill_tile_common(tp, m, true);
-    tp.qpart = pf->fc_q;
-    tp.ld_q = P;
-    tp.mu = pf->fc_mu;
-    tp.ld_mu = d;
-    launch_gp_tile(tp, d, true, s);
-  }
 }
 
 // Every launch of the roll-out.  per_filter_sums: k_fc_sum sums the new cloud and counts its
@@ -151,8 +61,8 @@ static int launch_rollout(gpmdm_pf* pf, int H, bool mean_only, bool obs, bool pe
   const long long P = pf->P, Pf = pf->Pf;
   const int nbf = (int)cdiv(Pf, 256);
   const std::vector<GpImage>& dset = m->dyn_set(true);   // every particle is evaluated: predict()'s images
-  const FcTables tb{pf->fc_tab};
-  double* out_ro = pf->fc_out + (size_t)H * F * (C + d);
+  const ClassTables tb{pf->fc_tab};
+  double* out_ro = pf->fc_out.dev + (size_t)H * F * (C + d);
   const double* Xcur = pf->X;
   const int* ccur = pf->cls;
   for (int h = 0; h < H; ++h) {
@@ -180,7 +90,9 @@ static int launch_rollout(gpmdm_pf* pf, int H, bool mean_only, bool obs, bool pe
       }
       fc_group(pf, ccur, s);
     }
-    fc_tiles(pf, Xcur, s);
+    // each class's dynamics GP on the scratch cloud, rows in the grouped order of fc_group
+    // (gpmdm_pf_predict's launches: every particle is evaluated)
+    launch_dyn_tiles(m, dset, dset[0].geo, tb.seg(), pf->fc_perm, Xcur, P, pf->fc_q, P, pf->fc_mu, s);
     FcFinishArgs fa{};
     fa.P = P;
     fa.Pf = Pf;
@@ -191,8 +103,8 @@ static int launch_rollout(gpmdm_pf* pf, int H, bool mean_only, bool obs, bool pe
     fa.frame = pf->frame;
     fa.seed_lo = seed_lo;
     fa.seed_hi = seed_hi;
-    fa.seg_out_base = tb.seg_out();
-    fa.seg_pos_begin = tb.seg_begin();
+    fa.seg_out_base = tb.seg().out();
+    fa.seg_pos_begin = tb.seg().begin();
     fa.perm = pf->fc_perm;
     for (int c = 0; c < C; ++c) fa.n_parts[c] = dset[c].n_parts();
     fa.qpart = pf->fc_q;
@@ -223,10 +135,10 @@ static int launch_rollout(gpmdm_pf* pf, int H, bool mean_only, bool obs, bool pe
     ra.n_count_rows = per_filter_sums ? nbf : 1;
     ra.counts = per_filter_sums ? pf->fc_bcounts : tb.counts();
     ra.partials = pf->fc_part;
-    ra.out = pf->fc_out + (size_t)h * F * (C + d);
+    ra.out = pf->fc_out.dev + (size_t)h * F * (C + d);
     launch_fc_reduce(ra, F, s);
     if (obs)                             // the step's pose: one read-out over the F clouds
-      launch_obs_readout(rollout_readout(pf, Xnext, pf->fc_ro_part, out_ro + (size_t)h * F * 2 * D), s);
+      launch_obs_readout(pose_readout(pf, Xnext, pf->fc_ro_part, out_ro + (size_t)h * F * 2 * D), s);
     Xcur = Xnext;
     HIPCHK(hipGetLastError());
   }
@@ -254,41 +166,34 @@ static int forecast(gpmdm_pf* pf, int horizon, int mode, const uint64_t* seed, c
   if (o.states || o.classes)
     CHECK((size_t)H * (size_t)P * (size_t)(d + 1) <= kForecastStageBytes / sizeof(double), stage_refusal);
   const unsigned long long sd = seed ? *seed : (((unsigned long long)pf->seed_hi << 32) | pf->seed_lo);
-  TRY(ensure_scratch(pf, H, obs, per_filter_sums));
+  TRY(ensure_scratch(pf, H, obs, per_filter_sums, s));
   // per-call staging of the clouds, released in the stream's order on every exit
-  double* stage_X = nullptr;
-  int* stage_cls = nullptr;
-  if (o.states) TRY(dalloc(&stage_X, (size_t)H * P * d));
-  if (o.classes && !mean_only && dalloc(&stage_cls, (size_t)H * P) != GPMDM_OK) {
-    dfree(stage_X);
-    return GPMDM_E_NOMEM;
-  }
+  DevBuf<double> stage_X;
+  DevBuf<int> stage_cls;
+  if (o.states) TRY(stage_X.alloc((size_t)H * P * d));
+  if (o.classes && !mean_only && stage_cls.alloc((size_t)H * P) != GPMDM_OK) return GPMDM_E_NOMEM;
   int rc = launch_rollout(pf, H, mean_only, obs, per_filter_sums, (unsigned)(sd & 0xffffffffu), (unsigned)(sd >> 32),
                           stage_X, stage_cls, s);
   const size_t n_rows = (size_t)H * F;
   const size_t n_out = n_rows * (C + d) + (obs ? n_rows * 2 * D : 0);
   std::vector<int> c32;
   auto copies = [&]() -> int {
-    HIPCHK(hipMemcpyAsync(pf->fc_pin, pf->fc_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pf->fc_out.pin, pf->fc_out.dev, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
     if (o.states) HIPCHK(hipMemcpyAsync(o.states, stage_X, sizeof(double) * H * P * d, hipMemcpyDeviceToHost, s));
     if (o.classes) {
       c32.resize((size_t)(mean_only ? 1 : H) * P);   // (mean mode: the filters' classes, every step)
-      HIPCHK(hipMemcpyAsync(c32.data(), mean_only ? pf->cls : stage_cls, sizeof(int) * c32.size(),
+      HIPCHK(hipMemcpyAsync(c32.data(), mean_only ? pf->cls.p : stage_cls.p, sizeof(int) * c32.size(),
                             hipMemcpyDeviceToHost, s));
     }
     return GPMDM_OK;
   };
   if (rc == GPMDM_OK) rc = copies();
-  const bool marked = hipEventRecord(pf->fc_ev, s) == hipSuccess;
-  pf->fc_pending = marked;               // (quiesce waits for the launches if the wait below fails)
-  if (stage_X) dfree_after(stage_X, s);
-  if (stage_cls) dfree_after(stage_cls, s);
-  if (rc != GPMDM_OK) return rc;
-  HIPCHK(hipStreamSynchronize(s));
-  pf->fc_pending = false;
-  const double* ro = pf->fc_pin + n_rows * (C + d);
+  stage_X.release_after(s);
+  stage_cls.release_after(s);
+  TRY(pf->fc_out.finish(rc, s));         // (quiesce waits for the launches if the wait fails)
+  const double* ro = pf->fc_out.pin + n_rows * (C + d);
   for (size_t q = 0; q < n_rows; ++q) {  // q = h * F + f
-    const double* row = pf->fc_pin + q * (C + d);
+    const double* row = pf->fc_out.pin + q * (C + d);
     if (o.class_prob) std::memcpy(o.class_prob + q * C, row, sizeof(double) * C);
     if (o.state_mean) std::memcpy(o.state_mean + q * d, row + C, sizeof(double) * d);
     if (o.obs_mean) std::memcpy(o.obs_mean + q * D, ro + q * 2 * D, sizeof(double) * D);

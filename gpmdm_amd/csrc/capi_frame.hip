@@ -11,7 +11,7 @@ namespace gpmdm::capi {
 static int check_counts(gpmdm_pf* pf) {
   if (!pf->cnt_check) return GPMDM_OK;
   // done: it precedes the resample already waited for (whose read-out number follows it)
-  HIPCHK(pf->seq_pin ? pf->wait_readout(pf->ro_seq) : hipEventSynchronize(pf->cnt_ev));
+  HIPCHK(pf->seq_pin ? pf->wait_readout(pf->ro_seq) : pf->cnt_ev.sync());
   pf->cnt_check = false;
   for (int c = 0; c < pf->m->C; ++c)
     if (pf->cnt_pin[c] != pf->cnt_expect[c])
@@ -86,33 +86,18 @@ int do_switch(gpmdm_pf* pf, const double* E, int64_t* class_counts, hipStream_t 
   sa.own = pf->own_order();
   pf->dyn_wide_frame = dyn_frame_wide(pf);
   pf->dyn_geo_frame = dyn_frame_geo(pf);
+  const SegTables sg = pf->tables().seg(), lsg = pf->ltables();
   ScanArgs sc{};
+  GroupArgs ga{};
+  fill_grouping(sc, ga, pf->tables(), pf->blockcounts, pf->blockoff, pf->perm, pf->cls_new, pf->P, C,
+                pf->dyn_geo_frame.pt());   // (tile unit of the dynamics pass)
+  // the switch's own: the slice it groups, in the ownership order
   sc.nb = nbs;
-  sc.C = C;
-  sc.pt = pf->dyn_geo_frame.pt();      // tile unit of the dynamics pass
   sc.lo = sl ? 0 : pf->lo;
   sc.hi = sl ? pf->nloc : pf->hi;
-  sc.own = pf->own_order();
-  sc.base = base;
-  sc.blockcounts = pf->blockcounts;
-  sc.cls_new = pf->cls_new;
-  sc.blockoff = pf->blockoff;
-  sc.class_start = pf->class_start();
-  sc.counts = pf->counts();
-  sc.seg_pos_begin = pf->seg_begin();
-  sc.seg_pos_end = pf->seg_end();
-  sc.seg_out_base = pf->seg_out();
-  sc.seg_tile_start = pf->seg_tiles();
-  GroupArgs ga{};
-  ga.P = pf->P;
-  ga.base = base;
+  sc.own = ga.own = pf->own_order();
+  sc.base = ga.base = base;
   ga.n = nsw;
-  ga.C = C;
-  ga.cls_new = pf->cls_new;
-  ga.class_start = pf->class_start();
-  ga.blockoff = pf->blockoff;
-  ga.own = pf->own_order();
-  ga.perm = pf->perm;
   LeadArgs la{};
   if (pf->dedup && pf->nloc > 0) {
     la.P = pf->P;
@@ -127,21 +112,21 @@ int do_switch(gpmdm_pf* pf, const double* E, int64_t* class_counts, hipStream_t 
     la.cls_new = pf->cls_new;
     la.anc = pf->ridx;
     la.owner = pf->owner;
-    la.seg_pos_begin = pf->seg_begin();
-    la.seg_pos_end = pf->seg_end();
+    la.seg_pos_begin = sg.begin();
+    la.seg_pos_end = sg.end();
     la.lflag_scan = pf->lflag;
     la.lblock = pf->lblock;
-    la.lseg_pos_begin = pf->lseg_begin();
-    la.lseg_pos_end = pf->lseg_end();
-    la.lseg_out_base = pf->lseg_out();
-    la.lseg_tile_start = pf->lseg_tiles();
+    la.lseg_pos_begin = lsg.begin();
+    la.lseg_pos_end = lsg.end();
+    la.lseg_out_base = lsg.out();
+    la.lseg_tile_start = lsg.tiles();
     la.lperm = pf->lperm;
     la.slot = pf->slot;
     la.owner_reset = pf->owner;        // restores the preset for the next election
   }
-  sc.counts_host = (class_counts || counts_ahead) ? pf->cnt_dev : nullptr;   // the counts straight to the host
+  sc.counts_host = (class_counts || counts_ahead) ? pf->cnt_pin.dev : nullptr;   // the counts straight to the host
   if (sc.counts_host && pf->cseq_pin) {
-    sc.counts_seq_host = pf->cseq_dev;
+    sc.counts_seq_host = pf->cseq_pin.dev;
     sc.counts_seq = pf->cseq + 1;
   }
   // the counts on the host (cls_pin): no wait for this switch
@@ -152,7 +137,7 @@ int do_switch(gpmdm_pf* pf, const double* E, int64_t* class_counts, hipStream_t 
   if (host_counts) {
     if (pf->cls_ev_pending) {          // the resample that wrote cls_pin (normally done: read)
       // (k_small_resample writes cls_pin before the read-out number it publishes)
-      HIPCHK(pf->seq_pin ? pf->wait_readout(pf->ro_seq) : hipEventSynchronize(pf->cls_ev));
+      HIPCHK(pf->seq_pin ? pf->wait_readout(pf->ro_seq) : pf->cls_ev.sync());
       pf->cls_ev_pending = false;
     }
     TRY(check_counts(pf));
@@ -190,7 +175,7 @@ int do_switch(gpmdm_pf* pf, const double* E, int64_t* class_counts, hipStream_t 
   HIPCHK(hipGetLastError());
   if (pf->rng_mode == GPMDM_RNG_REPLAY) HIPCHK(pf->draws_used(0, s));
   if (counts_ahead) {
-    if (!counts_by_seq) HIPCHK(hipEventRecord(pf->cnt_done, s));
+    if (!counts_by_seq) HIPCHK(pf->cnt_done.record(s));
     if (pf->nloc > 0) {
       launch_dyn_gemm(pf, s);
       HIPCHK(hipGetLastError());
@@ -199,24 +184,24 @@ int do_switch(gpmdm_pf* pf, const double* E, int64_t* class_counts, hipStream_t 
     pf->pre_counts = true;
     pf->pre_counts_seq = counts_by_seq;
   } else if (host_counts) {
-    if (!pf->seq_pin) HIPCHK(hipEventRecord(pf->cnt_ev, s));
+    if (!pf->seq_pin) HIPCHK(pf->cnt_ev.record(s));
     pf->cnt_check = true;
     for (int c = 0; c < C; ++c) class_counts[c] = pf->cnt_expect[c];
   } else if (class_counts) {
     int tmp[kMaxClasses];
     const int* src = pf->cnt_pin;
     if (!sc.counts_host) {
-      HIPCHK(hipMemcpyAsync(tmp, pf->counts(), sizeof(int) * C, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(tmp, pf->tables().counts(), sizeof(int) * C, hipMemcpyDeviceToHost, s));
       src = tmp;
     }
-    if (pf->cnt_done && pf->nloc > 0) {
+    if (pf->rng_mode == GPMDM_RNG_REPLAY && pf->nloc > 0) {
       // the dynamics-GP tiles need the switch's tables, not the normals the caller draws
       // from these counts: they run while it draws (propagate launches the finish only)
-      if (!counts_by_seq) HIPCHK(hipEventRecord(pf->cnt_done, s));
+      if (!counts_by_seq) HIPCHK(pf->cnt_done.record(s));
       launch_dyn_gemm(pf, s);
       HIPCHK(hipGetLastError());
       pf->gemm_ahead = true;
-      HIPCHK(counts_by_seq ? pf->wait_counts() : hipEventSynchronize(pf->cnt_done));
+      HIPCHK(counts_by_seq ? pf->wait_counts() : pf->cnt_done.sync());
     } else {
       HIPCHK(hipStreamSynchronize(s));
     }
@@ -226,16 +211,10 @@ int do_switch(gpmdm_pf* pf, const double* E, int64_t* class_counts, hipStream_t 
   return GPMDM_OK;
 }
 
-// The dynamics-GP tile launches of this rank's rows (per class, segments of at most kMaxSeg
-// classes per launch): narrow tiles for the de-duplicated rows, the wide image when every
-// particle is evaluated.  They need the switch's tables only, not the normals.
-static void launch_dyn_gemm(gpmdm_pf* pf, hipStream_t s) {
-  gpmdm_model* m = pf->m;
+void launch_dyn_tiles(const gpmdm_model* m, const std::vector<GpImage>& dset, TileGeo geo, SegTables tb,
+                      const int* perm, const double* X, long long rows_ub, double* q, long long ld_q, double* mu,
+                      hipStream_t s) {
   const int C = m->C, d = m->d;
-  const long long nl = pf->nloc;
-  const std::vector<GpImage>& dset = m->dyn_set(pf->dyn_wide_frame);
-  hipEvent_t t0;
-  pf->mark_begin(s, GPMDM_STAGE_DYN_GEMM, t0);
   for (int c0 = 0; c0 < C; c0 += kMaxSeg) {
     const int ns = std::min(kMaxSeg, C - c0);
     TileParams tp{};
@@ -245,33 +224,36 @@ static void launch_dyn_gemm(gpmdm_pf* pf, hipStream_t s) {
       njm = std::max(njm, dset[c0 + k].n_j);
     }
     tp.n_seg = ns;
-    tp.geo = pf->dyn_geo_frame;      // tile starts computed on the device in units of pt
+    tp.geo = geo;                     // tile starts computed on the device in units of pt
     // an upper bound (the leaders' tile count is known on the device only): the empty
     // workgroups map last and exit at once (an exact grid read back measured no faster,
     // DESIGN.md §3 "Dynamics tiles")
-    tp.tiles_ub = (int)(cdiv(nl, tp.geo.pt()) + ns);
+    tp.tiles_ub = (int)(cdiv(rows_ub, geo.pt()) + ns);
     tp.n_j_max = njm;
-    if (pf->dedup) {                  // one row per (ancestor, class) leader
-      tp.seg_pos_begin = pf->lseg_begin() + c0;
-      tp.seg_pos_end = pf->lseg_end() + c0;
-      tp.seg_out_base = pf->lseg_out() + c0;
-      tp.seg_tile_start = pf->lseg_tiles() + c0;
-      tp.perm = pf->lperm;
-    } else {
-      tp.seg_pos_begin = pf->seg_begin() + c0;
-      tp.seg_pos_end = pf->seg_end() + c0;
-      tp.seg_out_base = pf->seg_out() + c0;
-      tp.seg_tile_start = pf->seg_tiles() + c0;
-      tp.perm = pf->perm;
-    }
-    tp.X = pf->X;
+    tp.seg_pos_begin = tb.begin() + c0;
+    tp.seg_pos_end = tb.end() + c0;
+    tp.seg_out_base = tb.out() + c0;
+    tp.seg_tile_start = tb.tiles() + c0;
+    tp.perm = perm;
+    tp.X = X;
     fill_tile_common(tp, m, true);
-    tp.qpart = pf->qdyn;
-    tp.ld_q = nl;
-    tp.mu = pf->mudyn;
+    tp.qpart = q;
+    tp.ld_q = ld_q;
+    tp.mu = mu;
     tp.ld_mu = d;
     launch_gp_tile(tp, d, true, s);
   }
+}
+
+// The dynamics-GP tile launches of this rank's rows: narrow tiles for the de-duplicated rows
+// (one row per (ancestor, class) leader), the wide image when every particle is evaluated.
+// They need the switch's tables only, not the normals.
+static void launch_dyn_gemm(gpmdm_pf* pf, hipStream_t s) {
+  hipEvent_t t0;
+  pf->mark_begin(s, GPMDM_STAGE_DYN_GEMM, t0);
+  launch_dyn_tiles(pf->m, pf->m->dyn_set(pf->dyn_wide_frame), pf->dyn_geo_frame,
+                   pf->dedup ? pf->ltables() : pf->tables().seg(), pf->dedup ? pf->lperm : pf->perm, pf->X, pf->nloc,
+                   pf->qdyn, pf->nloc, pf->mudyn, s);
   pf->mark_end(s, GPMDM_STAGE_DYN_GEMM, t0);
 }
 
@@ -308,8 +290,8 @@ int propagate_dynamics(gpmdm_pf* pf, const double* normals, hipStream_t s, bool 
     fa.frame = pf->frame;
     fa.seed_lo = pf->seed_lo;
     fa.seed_hi = pf->seed_hi;
-    fa.seg_out_base = pf->seg_out();
-    fa.seg_pos_begin = pf->seg_begin();
+    fa.seg_out_base = pf->tables().seg().out();
+    fa.seg_pos_begin = pf->tables().seg().begin();
     fa.perm = pf->perm;
     for (int c = 0; c < C; ++c) fa.n_parts[c] = dset[c].n_parts();
     fa.qpart = pf->qdyn;
@@ -329,13 +311,14 @@ int propagate_dynamics(gpmdm_pf* pf, const double* normals, hipStream_t s, bool 
     fa.health = pf->health;
     fa.gmax_reset = pf->gmax;
     fa.F = pf->F;
-    fa.rows_b = pf->dedup ? pf->lseg_begin() : pf->seg_begin();
-    fa.rows_e = pf->dedup ? pf->lseg_end() : pf->seg_end();
+    const SegTables rows = pf->dedup ? pf->ltables() : pf->tables().seg();
+    fa.rows_b = rows.begin();
+    fa.rows_e = rows.end();
     fa.n_rows_seg = C;
     fa.rows_out = pf->rows_last();
-    fa.rows_host = pf->rows_pdev;
+    fa.rows_host = pf->rows_pin.dev;
     if (zstage) {
-      fa.z_src = pf->zdev[pf->zslot];
+      fa.z_src = pf->zpin[pf->zslot].dev;
       fa.z_dst = pf->z;
       fa.z_n = (long long)m->D * pf->F;
       pf->z_staged = true;
@@ -344,7 +327,7 @@ int propagate_dynamics(gpmdm_pf* pf, const double* normals, hipStream_t s, bool 
     pf->mark_end(s, GPMDM_STAGE_DYN_FINISH, t0);
   } else {
     // no particles on this rank: the maxima reset and row count k_dyn_finish would do
-    static const unsigned long long kNegInf[1] = {0x000fffffffffffffull};   // ord_enc(-inf)
+    static const unsigned long long kNegInf[1] = {host_ord_enc(-INFINITY)};
     for (int f = 0; f < pf->F; ++f)
       HIPCHK(hipMemcpyAsync(pf->gmax + f, kNegInf, sizeof(kNegInf), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(pf->rows_last(), 0, sizeof(int), s));
@@ -355,7 +338,7 @@ int propagate_dynamics(gpmdm_pf* pf, const double* normals, hipStream_t s, bool 
     // rep_ev[1] themselves), else the copy / the in-place reads above (one record fewer
     // between the dynamics finish and the observation GP when staged)
     if (!pf->n_staged_frame) HIPCHK(pf->draws_used(1, s));
-    if (pf->ndev_ev) HIPCHK(hipEventRecord(pf->ndev_ev, s));
+    if (pf->up_stream) HIPCHK(pf->ndev_ev.record(s));
   }
   pf->dyn_done = true;
   pf->switched = false;
@@ -402,7 +385,7 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
     HIPCHK(pf->zslot_free());
     pf->stage_z(pf->zpin[zk], zh);
     if (zmap)
-      zsrc = pf->zdev[zk];
+      zsrc = pf->zpin[zk].dev;
     else
       HIPCHK(hipMemcpyAsync(pf->z, pf->zpin[zk], sizeof(double) * D * pf->F, hipMemcpyHostToDevice, s));
     pf->zslot ^= 1;
@@ -433,13 +416,7 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
     // (mode 1 measures its reach the same way, for the split policy's chunk grid)
     bool auto_frame = false;
     if (cut && pf->cut_measure_active() && !small_resample_ok(norm_args(pf), resample_args(pf))) {
-      if (pf->cut_auto_pending) {      // the last cutoff frame's counters, published with its read-out
-        HIPCHK(pf->wait_readout(pf->cut_auto_seq));
-        const unsigned long long run = __atomic_load_n(pf->cut_auto_host + 0, __ATOMIC_ACQUIRE);
-        const unsigned long long dense = __atomic_load_n(pf->cut_auto_host + 1, __ATOMIC_ACQUIRE);
-        pf->cut_auto_frac = dense ? (double)run / (double)dense : 0.0;
-        pf->cut_auto_pending = false;
-      }
+      HIPCHK(pf->cut_auto_collect());
       if (pf->cut_auto) {
         const bool probe = pf->cut_auto_frac < 0.0 || (long long)pf->frame - pf->cut_auto_probe >= gpmdm_pf::kCutAutoProbe;
         cut = probe || pf->cut_auto_frac <= gpmdm_pf::kCutAutoMaxRun;
@@ -555,7 +532,7 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
     oa.z = zsrc;
     oa.Pf = pf->Pf;
     oa.il2 = m->y_il2_dev;
-    oa.ll_const = (double)((float)(0.5 * D) * (float)1.8378770351409912);
+    oa.ll_const = ll_const(D);
     if (masked) {
       oa.D = pf->D_obs;
       oa.sum_log_il2 = pf->sum_log_il2_obs;
@@ -625,17 +602,17 @@ int gpmdm_pf_switch(gpmdm_pf_t pf, const double* E, int64_t* class_counts, void*
     TRY(drop_preswitch(pf, s, false));   // other draws than the pre-switch's: switch again
   if (pf->preswitched) {               // launched by the last resample / gpmdm_pf_preswitch: consume it
     if (s != pf->sw_stream) {
-      HIPCHK(hipEventRecord(pf->sw_ev, pf->sw_stream));
-      HIPCHK(hipStreamWaitEvent(s, pf->sw_ev, 0));
+      HIPCHK(pf->sw_ev.record(pf->sw_stream));
+      HIPCHK(pf->sw_ev.block(s));
     }
     pf->preswitched = false;
     if (class_counts && pf->pre_counts) {
       // the counts, not the tiles behind them
-      HIPCHK(pf->pre_counts_seq ? pf->wait_counts() : hipEventSynchronize(pf->cnt_done));
+      HIPCHK(pf->pre_counts_seq ? pf->wait_counts() : pf->cnt_done.sync());
       for (int c = 0; c < pf->m->C; ++c) class_counts[c] = pf->cnt_pin[c];
     } else if (class_counts) {
       int tmp[kMaxClasses];
-      HIPCHK(hipMemcpyAsync(tmp, pf->counts(), sizeof(int) * pf->m->C, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(tmp, pf->tables().counts(), sizeof(int) * pf->m->C, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
       for (int c = 0; c < pf->m->C; ++c) class_counts[c] = tmp[c];
     }
@@ -681,8 +658,8 @@ int gpmdm_pf_resample(gpmdm_pf_t pf, const double* uniforms, void* stream) {
       // `stream` behind the GP would hold the next frame's draws (queued on up_stream after
       // it) back until the GP ends.  upload_draws first waits for the last resample.
       HIPCHK(pf->upload_draws(2, pf->U, uniforms, sys ? 1 : (size_t)pf->P, pf->up_stream));
-      HIPCHK(hipEventRecord(pf->up_ev, pf->up_stream));
-      HIPCHK(hipStreamWaitEvent(s, pf->up_ev, 0));
+      HIPCHK(pf->up_ev.record(pf->up_stream));
+      HIPCHK(pf->up_ev.block(s));
     } else {
       HIPCHK(pf->upload_draws(2, pf->U, uniforms, sys ? 1 : (size_t)pf->P, s));
     }
@@ -691,7 +668,7 @@ int gpmdm_pf_resample(gpmdm_pf_t pf, const double* uniforms, void* stream) {
   pf->mark_begin(s, GPMDM_STAGE_RESAMPLE, t0);
   ResampleArgs ra = resample_args(pf);
   if (pf->seq_pin) {                   // the read-out's number, published after it
-    ra.seq_host = pf->seq_dev;
+    ra.seq_host = pf->seq_pin.dev;
     ra.seq = ++pf->ro_seq;
     pf->ro_stream = s;
   }
@@ -718,11 +695,11 @@ int gpmdm_pf_resample(gpmdm_pf_t pf, const double* uniforms, void* stream) {
   }
   pf->rows_st = pf->rows_ll = nullptr;
   const bool cls_host = pf->cls_pin && small;
-  if (cls_host) ra.cls_host = pf->cls_pdev;
+  if (cls_host) ra.cls_host = pf->cls_pin.dev;
   const bool auto_stats = pf->cut_frame_auto && !small && pf->seq_pin;
   if (auto_stats) {                    // this frame's cutoff counters travel with the read-out
     ra.cut_stats = pf->cut_auto_dev;
-    ra.cut_stats_host = pf->cut_auto_hdev;
+    ra.cut_stats_host = pf->cut_auto_host.dev;
   }
   pf->cut_frame_auto = false;
   launch_normalise_resample(na, ra, s);
@@ -733,7 +710,7 @@ int gpmdm_pf_resample(gpmdm_pf_t pf, const double* uniforms, void* stream) {
   pf->bmax_ready = false;
   pf->cls_host_ok = cls_host;
   if (cls_host) {
-    if (!pf->seq_pin) HIPCHK(hipEventRecord(pf->cls_ev, s));
+    if (!pf->seq_pin) HIPCHK(pf->cls_ev.record(s));
     pf->cls_ev_pending = true;
   }
   pf->ll_pending = false;
@@ -757,7 +734,7 @@ int gpmdm_pf_resample(gpmdm_pf_t pf, const double* uniforms, void* stream) {
   pf->mark_end(s, GPMDM_STAGE_RESAMPLE, t0);
   HIPCHK(hipGetLastError());
   if (!pf->seq_pin) {                  // (else the read-out kernel publishes its number)
-    HIPCHK(hipEventRecord(pf->ro_ev, s));
+    HIPCHK(pf->ro_ev.record(s));
     pf->ro_ev_ok = true;
   }
   pf->frame += 1;
@@ -798,11 +775,11 @@ int gpmdm_pf_read(gpmdm_pf_t pf, double* post, double* mean, double* lik, void* 
   } else if (pf->seq_pin) {
     HIPCHK(pf->wait_readout(pf->ro_seq));     // not the stream: a pre-switch may follow
   } else if (pf->ro_ev_ok) {
-    HIPCHK(hipEventSynchronize(pf->ro_ev));   // not the stream: a pre-switch may follow
+    HIPCHK(pf->ro_ev.sync());                 // not the stream: a pre-switch may follow
   } else {
     HIPCHK(hipStreamSynchronize(s));
   }
-  pf->rows_hint = __atomic_load_n(pf->rows_pin, __ATOMIC_RELAXED);   // its dynamics pass has run (the read-out follows it)
+  pf->rows_hint = __atomic_load_n(pf->rows_pin.p, __ATOMIC_RELAXED);   // its dynamics pass has run (the read-out follows it)
   for (int f = 0; f < pf->F; ++f) {
     const double* b = src + (size_t)f * nr;
     if (post) std::memcpy(post + (size_t)f * m->C, b, sizeof(double) * m->C);

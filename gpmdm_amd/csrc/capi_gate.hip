@@ -14,7 +14,7 @@ int gate_rebind(gpmdm_pf* pf) {
   const int D = m->D;
   // the last frame's finish may still read the table: it precedes the frame's read-out
   HIPCHK(pf->zslot_free());
-  if (!pf->gt_lil) TRY(dalloc(&pf->gt_lil, (size_t)D));
+  if (!pf->gt_lil) TRY(pf->gt_lil.alloc((size_t)D));
   std::vector<double> lil((size_t)D);
   for (int j = 0; j < D; ++j) lil[(size_t)j] = std::log(m->y_il2[(size_t)j]);   // capi_pf.hip install_obs_mask's terms
   return h2d(pf->gt_lil, lil.data(), sizeof(double) * D);
@@ -35,9 +35,9 @@ static int set_gate(gpmdm_pf* pf, double threshold, double limit) {
   pf->gt_ready = false;
   const int D = pf->m->D;
   const size_t n_tab = gate_tab_doubles(D);
-  if (!pf->gt_tab) TRY(dalloc(&pf->gt_tab, n_tab));
-  if (!pf->gt_out) TRY(dalloc(&pf->gt_out, innov_out_doubles(D, 1)));
-  if (!pf->gt_pin) TRY(halloc(&pf->gt_pin, n_tab, 0));
+  if (!pf->gt_tab) TRY(pf->gt_tab.alloc(n_tab));
+  if (!pf->gt_out) TRY(pf->gt_out.alloc(innov_out_doubles(D, 1)));
+  if (!pf->gt_pin) TRY(pf->gt_pin.alloc(n_tab));
   const double was = pf->gate_k;
   pf->gate_k = threshold;
   const int rc = gate_rebind(pf);
@@ -57,13 +57,13 @@ int gate_frame(gpmdm_pf* pf, hipStream_t s) {
   pf->gt_ready = true;
   if (pf->gt_host) return GPMDM_OK;
   TRY(flush_ll(pf, s));                // a deferred finish has produced neither ll nor vc yet
-  TRY(grow(pf->gt_part, pf->gt_part_cap, innov_part_doubles(P, D, 1), s));
-  TRY(grow(pf->gt_sp, pf->gt_sp_cap, (size_t)readout_groups(D) * (size_t)P, s));
+  TRY(pf->gt_part.grow(innov_part_doubles(P, D, 1), s));
+  TRY(pf->gt_sp.grow((size_t)readout_groups(D) * (size_t)P, s));
   InnovParams ip{};
-  ip.ro = rollout_readout(pf, pf->X_prop, nullptr, nullptr);
+  ip.ro = pose_readout(pf, pf->X_prop, nullptr, nullptr);
   ip.vc = pf->vc_prop;
   ip.z = pf->pv_z;
-  ip.mask = pf->pv_masked ? pf->pv_mask_dev : nullptr;
+  ip.mask = pf->pv_masked ? pf->pv_mask.dev : nullptr;
   ip.il2 = m->y_il2_dev;
   ip.lam2 = m->y_lam2_dev;
   ip.part = pf->gt_part;
@@ -84,7 +84,7 @@ int gate_frame(gpmdm_pf* pf, hipStream_t s) {
   gp.tab = pf->gt_tab;
   gp.Sp = pf->gt_sp;
   gp.ll = pf->ll;
-  gp.bmax = pf->bmax_ready ? pf->bmax : nullptr;   // (else the normaliser takes the maximum from ll itself)
+  gp.bmax = pf->bmax_ready ? pf->bmax.p : nullptr;   // (else the normaliser takes the maximum from ll itself)
   launch_gate(gp, s);
   HIPCHK(hipGetLastError());
   return GPMDM_OK;

@@ -10,11 +10,7 @@
 namespace gpmdm::capi {
 
 int iv_wait(gpmdm_pf* pf) {
-  if (pf->iv_pending) {
-    HIPCHK(hipEventSynchronize(pf->iv_ev));
-    pf->iv_pending = false;
-  }
-  return GPMDM_OK;
+  return pf->iv_out.wait();
 }
 
 static int set_predictive(gpmdm_pf* pf, int on) {
@@ -29,17 +25,11 @@ static int set_predictive(gpmdm_pf* pf, int on) {
   pf->pv_clear();
   pf->predictive = false;
   if (!on) {
-    dfree(pf->vc_prop);
+    pf->vc_prop.release();
     return GPMDM_OK;
   }
-  if (!pf->iv_ev) HIPCHK(hipEventCreateWithFlags(&pf->iv_ev, hipEventDisableTiming));
-  if (!pf->vc_prop) TRY(dalloc(&pf->vc_prop, (size_t)pf->P));
-  if (!pf->pv_mask) {
-    void* mv = nullptr;
-    TRY(halloc(&pf->pv_mask, (size_t)pf->F * m->D, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(&mv, pf->pv_mask, 0));
-    pf->pv_mask_dev = (unsigned char*)mv;
-  }
+  if (!pf->vc_prop) TRY(pf->vc_prop.alloc((size_t)pf->P));
+  if (!pf->pv_mask) TRY(pf->pv_mask.alloc_mapped((size_t)pf->F * m->D));
   pf->predictive = true;
   return GPMDM_OK;
 }
@@ -67,47 +57,36 @@ static int innovation(gpmdm_pf* pf, const gpmdm_innovation_out* out, void* strea
   else
     HIPCHK(pf->zslot_free());          // the frame's launches, whatever stream they ran on
   const size_t n_out = innov_out_doubles(D, F);
-  TRY(grow(pf->iv_part, pf->iv_part_cap, innov_part_doubles(Pf, D, F), s));
-  if (pf->iv_out_cap < n_out) {
-    hfree(pf->iv_pin);
-    TRY(grow(pf->iv_out, pf->iv_out_cap, n_out, s));
-    TRY(halloc(&pf->iv_pin, n_out, 0));
-  }
+  TRY(pf->iv_part.grow(innov_part_doubles(Pf, D, F), s));
+  TRY(pf->iv_out.reserve(n_out, s));
   const size_t n_tile_part = (size_t)F * readout_tiles(Pf) * readout_groups(D) * kRoGC * kInnovPlanes;
   InnovParams ip{};
-  ip.ro = rollout_readout(pf, pf->X_prop, nullptr, nullptr);
+  ip.ro = pose_readout(pf, pf->X_prop, nullptr, nullptr);
   ip.vc = pf->pv_has_vc ? pf->vc_prop : nullptr;
   ip.z = pf->pv_z;
-  ip.mask = pf->pv_masked ? pf->pv_mask_dev : nullptr;
+  ip.mask = pf->pv_masked ? pf->pv_mask.dev : nullptr;
   ip.il2 = m->y_il2_dev;
   ip.lam2 = m->y_lam2_dev;
   ip.part = pf->iv_part;
   ip.vpart = pf->iv_part + n_tile_part;
-  ip.out = pf->iv_out;
+  ip.out = pf->iv_out.dev;
+  launch_obs_innov(ip, s);
   if (!out) {                          // launched only (timing): the handle's lifecycle waits for it
-    launch_obs_innov(ip, s);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(pf->iv_ev, s));
-    pf->iv_pending = true;
-    return GPMDM_OK;
+    return pf->iv_out.leave_pending(s);
   }
-  auto launches = [&]() -> int {
-    launch_obs_innov(ip, s);
+  auto copies = [&]() -> int {
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(pf->iv_pin, pf->iv_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pf->iv_out.pin, pf->iv_out.dev, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
     if (o.states) HIPCHK(hipMemcpyAsync(o.states, pf->X_prop, sizeof(double) * P * d, hipMemcpyDeviceToHost, s));
     if (o.variance_common && pf->pv_has_vc)
       HIPCHK(hipMemcpyAsync(o.variance_common, pf->vc_prop, sizeof(double) * P, hipMemcpyDeviceToHost, s));
     return GPMDM_OK;
   };
-  const int rc = launches();
-  pf->iv_pending = hipEventRecord(pf->iv_ev, s) == hipSuccess;   // (quiesce waits if the wait below fails)
-  if (rc != GPMDM_OK) return rc;
-  HIPCHK(hipStreamSynchronize(s));
-  pf->iv_pending = false;
+  TRY(pf->iv_out.finish(copies(), s));   // (quiesce waits for the launches if the wait fails)
   double* const fields[kInnovFields] = {o.mean, o.spread, o.gp_variance, o.variance, o.residual, o.zscore, o.log_density};
   for (int f = 0; f < F; ++f) {
-    const double* row = pf->iv_pin + (size_t)f * (kInnovFields * D + 1);
+    const double* row = pf->iv_out.pin + (size_t)f * (kInnovFields * D + 1);
     for (int k = 0; k < kInnovFields; ++k)
       if (fields[k]) std::memcpy(fields[k] + (size_t)f * D, row + (size_t)k * D, sizeof(double) * D);
     if (o.n_valid) o.n_valid[f] = (int64_t)row[(size_t)kInnovFields * D];
@@ -133,12 +112,8 @@ static int observation_gp(gpmdm_pf* pf, double* gp_var, void* stream) {
   const int D = m->D, F = pf->F;
   const size_t n_out = (size_t)F * D, nbf = (size_t)cdiv(pf->Pf, 256);
   HIPCHK(pf->zslot_free());            // the frame's resample, whatever stream it ran on
-  TRY(grow(pf->iv_part, pf->iv_part_cap, (size_t)F * nbf * 2, s));
-  if (pf->iv_out_cap < n_out) {
-    hfree(pf->iv_pin);
-    TRY(grow(pf->iv_out, pf->iv_out_cap, n_out, s));
-    TRY(halloc(&pf->iv_pin, n_out, 0));
-  }
+  TRY(pf->iv_part.grow((size_t)F * nbf * 2, s));
+  TRY(pf->iv_out.reserve(n_out, s));
   VcGatherArgs ga{};
   ga.Pf = pf->Pf;
   ga.D = D;
@@ -146,26 +121,19 @@ static int observation_gp(gpmdm_pf* pf, double* gp_var, void* stream) {
   ga.ridx = pf->ridx;
   ga.il2 = m->y_il2_dev;
   ga.partials = pf->iv_part;
-  ga.out = pf->iv_out;
+  ga.out = pf->iv_out.dev;
+  launch_vc_gather(ga, F, s);
   if (!gp_var) {                       // launched only (timing)
-    launch_vc_gather(ga, F, s);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(pf->iv_ev, s));
-    pf->iv_pending = true;
-    return GPMDM_OK;
+    return pf->iv_out.leave_pending(s);
   }
-  auto launches = [&]() -> int {
-    launch_vc_gather(ga, F, s);
+  auto copy = [&]() -> int {
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(pf->iv_pin, pf->iv_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pf->iv_out.pin, pf->iv_out.dev, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
     return GPMDM_OK;
   };
-  const int rc = launches();
-  pf->iv_pending = hipEventRecord(pf->iv_ev, s) == hipSuccess;
-  if (rc != GPMDM_OK) return rc;
-  HIPCHK(hipStreamSynchronize(s));
-  pf->iv_pending = false;
-  std::memcpy(gp_var, pf->iv_pin, sizeof(double) * n_out);
+  TRY(pf->iv_out.finish(copy(), s));
+  std::memcpy(gp_var, pf->iv_out.pin, sizeof(double) * n_out);
   return GPMDM_OK;
 }
 

@@ -1,9 +1,18 @@
 // Internal interface of the C-ABI translation units (capi_*.hip): the model and filter
 // handles (device layout, per-frame bookkeeping) and the helpers the units share.  Not part of
 // the public ABI (include/gpmdm_hip.h).
+// Ownership: both handles hold their device buffers, pinned buffers and events in status.h's
+// owning types (DevBuf, PinBuf, Event), released by the members' destructors; the handles'
+// own destructors keep only what has an order (side streams drained first).  The read-outs
+// whose results land in a pinned buffer are status.h Landing objects, which also carry the
+// pending event the lifecycle waits (quiesce) go through.  What several units fill the same
+// way has one builder here: the class-table layout (ClassTables / SegTables), fill_grouping,
+// launch_dyn_tiles, pose_readout, ll_const, host_ord_enc / host_ord_dec.
 //   capi_model.hip     models, predictive maps (gpmdm_model_*, gpmdm_predict_*), images
-//   capi_pf.hip        filter and bank lifecycle, state import / export, settings, predict
-//   capi_frame.hip     the per-frame launch sequence: switch, propagate, weigh, resample, read
+//   capi_pf.hip        filter and bank lifecycle, state import / export, settings, predict,
+//                      the pose read-out (gpmdm_pf_observation) and the grouping arguments
+//   capi_frame.hip     the per-frame launch sequence: switch, propagate, weigh, resample, read;
+//                      the dynamics tile launches
 //   capi_exchange.hip  the multi-rank exchange (pack / unpack, RCCL communicator, gathers)
 //   capi_replay.hip    replay-draw staging (pinned buffers, staged normals, pre-switch)
 //   capi_forecast.hip  the multi-step forecast roll-out (gpmdm_pf_forecast, gpmdm_bank_forecast)
@@ -51,21 +60,53 @@ constexpr long long kWideRows = 4096;
 // classes).  The host loop is P x C fp64 divisions: ~1 us at the notebook's P = 100.
 constexpr long long kHostCountsMaxP = 1024;
 
+// The class-table layout (one definition: the step's tables small + 0, predict()'s
+// small + kPredictTables, the forecast's fc_tab; the leaders' ltab holds the segment part
+// only): arrays of kTabStride ints -- class_start, counts, then the four segment arrays the
+// dynamics tiles read.
+constexpr int kTabStride = 40;
+struct SegTables {
+  int* t;
+  int* begin() const { return t; }
+  int* end() const { return t + kTabStride; }
+  int* out() const { return t + 2 * kTabStride; }
+  int* tiles() const { return t + 3 * kTabStride; }
+};
+struct ClassTables {
+  int* t;
+  int* class_start() const { return t; }
+  int* counts() const { return t + kTabStride; }
+  SegTables seg() const { return SegTables{t + 2 * kTabStride}; }
+};
+
+// The host's side of common.h's order-preserving uint64 image of a double (ord_enc / ord_dec
+// there are device functions)
+inline unsigned long long host_ord_enc(double x) {
+  unsigned long long u;
+  std::memcpy(&u, &x, sizeof(u));
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+inline double host_ord_dec(unsigned long long u) {
+  const unsigned long long v = (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u;
+  double x;
+  std::memcpy(&x, &v, sizeof(x));
+  return x;
+}
+
+// The likelihood's constant 0.5 n log(2 pi) of n observed dimensions, rounded as the reference
+// rounds it (fp32 factors); the finish takes it as an argument
+inline double ll_const(int n_observed) { return (double)((float)(0.5 * n_observed) * (float)1.8378770351409912); }
+
 // One GP's device image: scaled inputs (+ squared norms) and B = [R | M] (+ H for the
 // dynamics GPs) in MFMA-fragment order -- layout and packing in host_image.h.
 struct GpImage {
   int n_rows = 0, n_m = 0, n_j = 0, coff = 0;
   bool dyn = false;       // a dynamics GP's image (linear-kernel rows H)
   TileGeo geo = kGeo64x256;
-  double* Xrec = nullptr; // row_cap(n_rows) x (d + 1) row records (host_image.h)
-  double* Hf = nullptr;   // dynamics only
-  double* Bf = nullptr;
+  DevBuf<double> Xrec;    // row_cap(n_rows) x (d + 1) row records (host_image.h)
+  DevBuf<double> Hf;      // dynamics only
+  DevBuf<double> Bf;
 
-  void release() {
-    dfree(Xrec);
-    dfree(Hf);
-    dfree(Bf);
-  }
   SegDesc seg() const {
     SegDesc s{};
     s.Xrec = Xrec;
@@ -124,13 +165,12 @@ struct gpmdm_model {
     for (auto& g : dynw) mx = std::max(mx, g.n_parts());
     return mx;
   }
-  double* y_il2_dev = nullptr;
-  double* y_lam2_dev = nullptr;   // 1 / il2 = exp(y_log_lambdas)^2
+  DevBuf<double> y_il2_dev;
+  DevBuf<double> y_lam2_dev;      // 1 / il2 = exp(y_log_lambdas)^2
   double sum_log_il2 = 0.0;
   // the filtered-pose read-out (obs_readout.h): beta = K_y^-1 Y in its own fragment order,
   // and the observation kernel's lengthscales on the device
-  double* ro_beta = nullptr;
-  double* y_ls_dev = nullptr;
+  DevBuf<double> ro_beta, y_ls_dev;
   // Observation-GP cutoff image (gpmdm_model_set_obs_cutoff; empty: not set): K^-1's block
   // upper triangle and M over the training rows in a spatial order, tile-major
   // (host_image.h CutoffPacker, obs_cutoff.h), the K-step spheres, and the cutoff (tau; cut2 =
@@ -138,20 +178,12 @@ struct gpmdm_model {
   // in the generation's exponent units)
   struct CutImage {
     int n_rows = 0, n_m = 0, T_R = 0, T_M = 0;
-    double* Xrec = nullptr;
-    double* Bt = nullptr;
-    long long* toff = nullptr;
-    double* sph = nullptr;
+    DevBuf<double> Xrec, Bt, sph;
+    DevBuf<long long> toff;
   } obs_cut;
   bool has_cutoff() const { return obs_cut.Bt != nullptr; }
   double cut_tau = 0.0, cut2 = 0.0, t_cut = 0.0;
-  void release_cutoff() {
-    dfree(obs_cut.Xrec);
-    dfree(obs_cut.Bt);
-    dfree(obs_cut.toff);
-    dfree(obs_cut.sph);
-    obs_cut = CutImage{};
-  }
+  void release_cutoff() { obs_cut = CutImage{}; }
 
   // Lifecycle (DESIGN.md §1 "Lifecycle waits"): the filters built on the model --
   // gpmdm_model_set_obs_cutoff waits for each one's own last frame (quiesce) before it
@@ -186,15 +218,7 @@ struct gpmdm_model {
       for (auto& u : uses) (void)hipStreamWaitEvent(life, u.second, 0);
     }
     for (auto& u : uses) (void)hipEventDestroy(u.second);
-    obs.release();
-    obs_small.release();
-    for (auto& g : dyn) g.release();
-    for (auto& g : dynw) g.release();
-    release_cutoff();
-    dfree(y_il2_dev);
-    dfree(y_lam2_dev);
-    dfree(ro_beta);
-    dfree(y_ls_dev);
+    // (the images and tables are released by their members' destructors, after these waits)
   }
 };
 
@@ -240,20 +264,20 @@ struct gpmdm_pf {
   // switch launches the dynamics-GP tiles (they need no normals) before it waits for the
   // counts, so they run while the host draws; propagate then launches the finish only
   bool gemm_ahead = false;
-  hipEvent_t cnt_done = nullptr;      // after the switch's class counts (replay, large filters)
+  Event cnt_done;                     // after the switch's class counts (replay, large filters)
   bool dedup = true;                  // ancestor de-duplication of the dynamics GP
   int dyn_tiles = GPMDM_DYN_TILES_AUTO;   // gpmdm_pf_set_dyn_tiles
   bool wide_dyn() const { return dyn_tiles == GPMDM_DYN_TILES_WIDE || (dyn_tiles == GPMDM_DYN_TILES_AUTO && !dedup); }
   bool dyn_wide_frame = false;        // this frame's dynamics image (set by the switch: dyn_frame_wide)
   // device state
-  double *T = nullptr, *X = nullptr, *X_prop = nullptr, *ll = nullptr;
-  int *cls = nullptr, *cls_new = nullptr, *perm = nullptr, *ridx = nullptr;
-  int *blockcounts = nullptr, *blockoff = nullptr, *small = nullptr;   // small: class tables
-  int *obs_tab = nullptr;            // [0, 5): the observation launch's segment table; [8, 13): the cutoff image's
+  DevBuf<double> T, X, X_prop, ll;
+  DevBuf<int> cls, cls_new, perm, ridx;
+  DevBuf<int> blockcounts, blockoff, small;   // small: class tables
+  DevBuf<int> obs_tab;               // [0, 5): the observation launch's segment table; [8, 13): the cutoff image's
   // the observation GP's kernel-value cutoff (gpmdm_pf_set_obs_cutoff): on, and the skip
   // statistics of the cutoff kernel (device: MFMA groups run, the dense kernel's count)
   bool obs_cutoff = false;
-  unsigned long long* sp_stats = nullptr;
+  DevBuf<unsigned long long> sp_stats;
   bool sp_stats_on = false;
   // AUTO (gpmdm_pf_set_obs_cutoff mode 3; single-rank filters and banks with mapped
   // read-outs): the cutoff kernel while the reach it measured is low, the dense kernel
@@ -264,9 +288,8 @@ struct gpmdm_pf {
   static constexpr int kCutAutoProbe = 8;
   static constexpr double kCutAutoMaxRun = 0.75;   // break-even: cutoff 0.65 vs dense 0.865 of peak
   bool cut_auto = false;
-  unsigned long long* cut_auto_dev = nullptr;      // device counters {run, dense}
-  unsigned long long* cut_auto_host = nullptr;     // mapped: the last cutoff frame's counters
-  unsigned long long* cut_auto_hdev = nullptr;     // (its device view)
+  DevBuf<unsigned long long> cut_auto_dev;         // device counters {run, dense}
+  PinBuf<unsigned long long> cut_auto_host;        // mapped: the last cutoff frame's counters
   bool cut_auto_pending = false;                   // a cutoff frame's counters are on their way
   long long cut_auto_seq = 0;                      // ... published with this read-out number
   double cut_auto_frac = -1.0;                     // the last measured fraction (< 0: none)
@@ -279,28 +302,27 @@ struct gpmdm_pf {
     return obs_cutoff && !sp_stats_on && n_ranks == 1 && seq_pin != nullptr && cut_auto_dev != nullptr;
   }
   bool cut_auto_active() const { return cut_auto && cut_measure_active(); }
+  // the last cutoff frame's counters, published with its read-out (as the next frame reads them)
+  hipError_t cut_auto_collect() {
+    if (!cut_auto_pending) return hipSuccess;
+    const hipError_t e = wait_readout(cut_auto_seq);
+    if (e != hipSuccess) return e;
+    const unsigned long long run = __atomic_load_n(cut_auto_host + 0, __ATOMIC_ACQUIRE);
+    const unsigned long long dense = __atomic_load_n(cut_auto_host + 1, __ATOMIC_ACQUIRE);
+    cut_auto_frac = dense ? (double)run / (double)dense : 0.0;
+    cut_auto_pending = false;
+    return hipSuccess;
+  }
   static constexpr double kCutChunksMin = 0.5;     // GPMDM_CUT_SPLIT_AUTO: the chunk grid from this reach
   // the cutoff kernel's split tiles (capi_frame.hip): second parts' partials, (n_act, c*) per
   // split tile; grown on demand
   int cut_split_policy = GPMDM_CUT_SPLIT_AUTO;
-  double* cut_part = nullptr;
-  size_t cut_part_cap = 0;
-  int2* cut_split = nullptr;
-  int cut_split_cap = 0;
+  DevBuf<double> cut_part;
+  DevBuf<int2> cut_split;
   // (grown inside a frame: the old buffers are released after the frame stream's earlier work)
   int ensure_cut_split(size_t n_part, int n_split, hipStream_t s) {
-    if (n_part > cut_part_cap) {
-      dfree_after(cut_part, s);
-      cut_part_cap = 0;
-      if (dalloc(&cut_part, n_part)) return fail(GPMDM_E_NOMEM, "cutoff split partials");
-      cut_part_cap = n_part;
-    }
-    if (n_split > cut_split_cap) {
-      dfree_after(cut_split, s);
-      cut_split_cap = 0;
-      if (dalloc(&cut_split, (size_t)n_split)) return fail(GPMDM_E_NOMEM, "cutoff split table");
-      cut_split_cap = n_split;
-    }
+    if (cut_part.grow(n_part, s)) return fail(GPMDM_E_NOMEM, "cutoff split partials");
+    if (cut_split.grow((size_t)n_split, s)) return fail(GPMDM_E_NOMEM, "cutoff split table");
     return GPMDM_OK;
   }
   // Masked observations (gpmdm_pf_set_obs_mask; obs_mask empty: every dimension observed).
@@ -316,7 +338,7 @@ struct gpmdm_pf {
   // lam2_obs in the same allocation (obs_ftab; one upload installs both).  D_obs is then the
   // sum over the filters (0: every filter blacked out) and the two scalars are unused.
   std::vector<unsigned char> obs_mask;
-  double* lam2_obs = nullptr;
+  DevBuf<double> lam2_obs;
   int D_obs = 0;
   double sum_log_il2_obs = 0.0, ll_const_obs = 0.0;
   bool masked() const { return !obs_mask.empty(); }
@@ -331,10 +353,9 @@ struct gpmdm_pf {
   }
   // The filtered-pose read-out (gpmdm_pf_observation, obs_readout.h): the tiles' partials,
   // the device result {mean, spread} and its pinned landing buffer, allocated on first use;
-  // ro_obs_ev follows the last read-out's launches (quiesce waits for it).
-  double *ro_part = nullptr, *ro_obs = nullptr, *ro_obs_pin = nullptr;
-  hipEvent_t ro_obs_ev = nullptr;
-  bool ro_obs_pending = false;
+  // ro_obs.ev follows the last read-out's launches (quiesce waits for it).
+  DevBuf<double> ro_part;
+  Landing ro_obs;
   // The forecast roll-out (gpmdm_pf_forecast / gpmdm_bank_forecast, forecast.h;
   // capi_forecast.hip): scratch of its own, allocated on first use -- the two halves of the
   // ping-pong cloud, the grouping's tables (the layout of `small`'s, base 0), block counts /
@@ -343,17 +364,13 @@ struct gpmdm_pf {
   // the pose read-out's partials, and the H x F x (C + d + 2 D) result rows with their pinned
   // landing buffer (grown on demand).  None
   // of it is shared with the step, the pre-switch, predict() or the read-out, so a forecast
-  // leaves a pending pre-switch pending.  fc_ev follows a forecast's launches (quiesce waits
-  // for it while fc_pending: the call itself synchronises, so only after a failed one).
-  double* fc_X[2] = {nullptr, nullptr};
-  int* fc_cls[2] = {nullptr, nullptr};
-  int *fc_perm = nullptr, *fc_blockcounts = nullptr, *fc_blockoff = nullptr, *fc_tab = nullptr, *fc_bcounts = nullptr;
-  double *fc_q = nullptr, *fc_mu = nullptr, *fc_part = nullptr, *fc_ro_part = nullptr;
-  size_t fc_q_cap = 0;
-  double *fc_out = nullptr, *fc_pin = nullptr;
-  size_t fc_out_cap = 0;
-  hipEvent_t fc_ev = nullptr;
-  bool fc_pending = false;
+  // leaves a pending pre-switch pending.  fc_out.ev follows a forecast's launches (quiesce waits
+  // for it while pending: the call itself synchronises, so only after a failed one).
+  DevBuf<double> fc_X[2];
+  DevBuf<int> fc_cls[2];
+  DevBuf<int> fc_perm, fc_blockcounts, fc_blockoff, fc_tab, fc_bcounts;
+  DevBuf<double> fc_q, fc_mu, fc_part, fc_ro_part;
+  Landing fc_out;
   // Fixed-lag smoothing (gpmdm_pf_set_smoothing / gpmdm_pf_smoothed and the banks', smooth.h;
   // capi_smooth.hip).  sm_L > 0: every resample records {ridx, cls, X} into slot
   // frame mod (sm_L + 1) of the ring (sm_anc / sm_cls / sm_X, sm_L + 1 frames each); sm_depth =
@@ -363,18 +380,17 @@ struct gpmdm_pf {
   // behind every record launch (smoothing on only) and quiesce waits for it while sm_pending.
   // The read-out's scratch -- marks with the class counts at their head, block sums, result rows with their pinned
   // landing buffer, the pose read-out's partials -- is its own, allocated on first use and grown
-  // on demand; sm_tr_ev follows a read-out's launches (waited for while sm_tr_pending: the call
+  // on demand; sm_out.ev follows a read-out's launches (waited for while pending: the call
   // itself synchronises, so only after a failed one).
   int sm_L = 0, sm_depth = 0;
-  int* sm_anc = nullptr;
-  int* sm_cls = nullptr;
-  double* sm_X = nullptr;
-  hipEvent_t sm_ev = nullptr, sm_tr_ev = nullptr;
+  DevBuf<int> sm_anc, sm_cls;
+  DevBuf<double> sm_X;
+  Event sm_ev;
   hipStream_t sm_stream = nullptr;    // the stream of the last record launch
-  bool sm_pending = false, sm_tr_pending = false;
-  double *sm_part = nullptr, *sm_out = nullptr, *sm_pin = nullptr, *sm_ro_part = nullptr;
-  unsigned char* sm_marks = nullptr;
-  size_t sm_part_cap = 0, sm_out_cap = 0, sm_marks_cap = 0;
+  bool sm_pending = false;
+  DevBuf<double> sm_part, sm_ro_part;
+  Landing sm_out;
+  DevBuf<unsigned char> sm_marks;
   int sm_slot() const { return (int)(frame % (unsigned)(sm_L + 1)); }   // the latest frame's
   // Innovations and the GP's predictive variance (gpmdm_pf_set_predictive, gpmdm_pf_innovation,
   // gpmdm_pf_observation_gp and the banks'; obs_innov.h, capi_innov.hip).  predictive: every
@@ -386,15 +402,13 @@ struct gpmdm_pf {
   // propagate, init, import, rebind or set_predictive (pv_has_vc: an observation kernel ran
   // for it, i.e. no single-filter blackout); pv_resampled: that frame's resample has completed,
   // so vc_prop[ridx] is the resampled cloud's.  The calls' scratch is their own, grown on
-  // demand; iv_ev follows their launches (quiesce waits for it while iv_pending).
+  // demand; iv_out.ev follows their launches (quiesce waits for it while pending).
   bool predictive = false, pv_weighed = false, pv_has_vc = false, pv_resampled = false, pv_masked = false;
-  double* vc_prop = nullptr;
+  DevBuf<double> vc_prop;
   const double* pv_z = nullptr;
-  unsigned char *pv_mask = nullptr, *pv_mask_dev = nullptr;
-  double *iv_part = nullptr, *iv_out = nullptr, *iv_pin = nullptr;
-  size_t iv_part_cap = 0, iv_out_cap = 0;
-  hipEvent_t iv_ev = nullptr;
-  bool iv_pending = false;
+  PinBuf<unsigned char> pv_mask;
+  DevBuf<double> iv_part;
+  Landing iv_out;
   void pv_clear() { pv_weighed = pv_has_vc = pv_resampled = gt_ready = false; }
   // Outlier gating inside the frame (gpmdm_pf_set_gate, gpmdm_pf_gate_report; obs_gate.h,
   // capi_gate.hip).  gate_k > 0: on (single filters on one rank, predictive on): weigh ends with
@@ -408,8 +422,8 @@ struct gpmdm_pf {
   // host's).
   double gate_k = 0.0, gate_limit = 0.5;
   bool gt_ready = false, gt_host = false;
-  double *gt_part = nullptr, *gt_out = nullptr, *gt_tab = nullptr, *gt_sp = nullptr, *gt_lil = nullptr, *gt_pin = nullptr;
-  size_t gt_part_cap = 0, gt_sp_cap = 0;
+  DevBuf<double> gt_part, gt_out, gt_tab, gt_sp, gt_lil;
+  PinBuf<double> gt_pin;
   // likelihood finish deferred into the resampling launch (single-shard small filters:
   // k_small_resample computes ll first, one launch less per frame); flush_ll runs it for
   // any reader of ll that comes first
@@ -417,24 +431,23 @@ struct gpmdm_pf {
   ObsFinishArgs oa_pending{};
   const GpImage* obs_img = nullptr;   // the observation launch's image and shape (obs_pick)
   TileGeo obs_geo{};
-  int* guide = nullptr;             // F x (GB + 3) inverse-CDF guide table
-  int *sys_mark = nullptr, *sys_block = nullptr;   // systematic resampling by scan (pf_kernels.hip)
+  DevBuf<int> guide;                // F x (GB + 3) inverse-CDF guide table
+  DevBuf<int> sys_mark, sys_block;  // systematic resampling by scan (pf_kernels.hip)
   // ancestor de-duplication: owner/slot are C x P keyed by (class, ancestor)
-  unsigned* owner = nullptr;
-  int *slot = nullptr, *lflag = nullptr, *lblock = nullptr, *ltab = nullptr, *lperm = nullptr;
+  DevBuf<unsigned> owner;
+  DevBuf<int> slot, lflag, lblock, ltab, lperm;
   // ancestor-ordered shards (multi-rank philox filters, shard_order.hip): own = particles
   // in order of their resampling uniform's bucket; this rank evaluates positions [lo, hi)
-  int* own = nullptr;
-  int* own_inv = nullptr;            // own_inv[own[r]] = r
-  unsigned char* own_tmp = nullptr;
+  DevBuf<int> own;
+  DevBuf<int> own_inv;               // own_inv[own[r]] = r
+  DevBuf<unsigned char> own_tmp;
   size_t own_tmp_bytes = 0;
   bool own_valid = false;
   bool shard_order = true;            // gpmdm_pf_set_shard_order
   // The order a resample installs depends only on (seed, frame), so the pre-switch computes
   // the next resample's order into own_next / inv_next behind the read-out (the GPU's gap
   // while the host takes the outputs); that resample swaps it in instead of computing it.
-  int* own_next = nullptr;
-  int* inv_next = nullptr;
+  DevBuf<int> own_next, inv_next;
   long long own_next_frame = -1;     // the frame own_next was computed for (-1: none)
   // (single-rank filters keep it only with the observation-GP cutoff: particles of one
   // resampling-ancestor range form compact tiles, which skip more of the cutoff's K-steps)
@@ -455,9 +468,8 @@ struct gpmdm_pf {
   const int* rows_inv = nullptr;     // the ownership order the rows were gathered in (nullptr: identity)
   // observation upload through two pinned slots (a pageable hipMemcpyAsync is staged by the
   // runtime and stalls the launching thread); each slot's event guards its reuse
-  double* zpin[2] = {nullptr, nullptr};
-  const double* zdev[2] = {nullptr, nullptr};   // device views of zpin (small z read in place)
-  double* rpin = nullptr;             // pinned read-out landing buffer (F x (C + d + 1))
+  PinBuf<double> zpin[2];             // mapped (small z read in place)
+  PinBuf<double> rpin;                // pinned read-out landing buffer (F x (C + d + 1))
   // replay-mode draws (E, normals, U) staged through pinned buffers: the caller's arrays are
   // free for reuse when the call returns, whatever the runtime does with pageable copies;
   // each buffer's event guards its reuse
@@ -465,21 +477,20 @@ struct gpmdm_pf {
   // kernels read them from the mapped pinned buffer (a copy is a launch of its own, ~4 us
   // on the frame's critical path).  rep_src[k] is what the kernels read this frame; the
   // event, recorded after the consuming launches (draws_used), guards the buffer's reuse.
-  double* rep_pin[3] = {nullptr, nullptr, nullptr};
-  const double* rep_dev[3] = {nullptr, nullptr, nullptr};   // device view of rep_pin
+  PinBuf<double> rep_pin[3];          // mapped
   const double* rep_src[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t rep_ev[3] = {nullptr, nullptr, nullptr};
+  Event rep_ev[3];
   static constexpr size_t kZeroCopyBytes = 32768;
   hipError_t upload_draws(int k, double* dst, const double* src, size_t n, hipStream_t s) {
     // the buffer's previous readers have run (kernels that read it in place: guarded by the
     // read-out number of the frame that read it, see draws_used)
-    const bool in_place = sizeof(double) * n <= kZeroCopyBytes && rep_dev[k];
-    hipError_t e = in_place && seq_pin ? wait_readout(ro_seq) : hipEventSynchronize(rep_ev[k]);
+    const bool in_place = sizeof(double) * n <= kZeroCopyBytes && rep_pin[k].dev;
+    hipError_t e = in_place && seq_pin ? wait_readout(ro_seq) : rep_ev[k].sync();
     if (e != hipSuccess) return e;
     // draws written straight into the staging buffer (gpmdm_pf_draw_buffers): no copy
     if (src != rep_pin[k]) std::memcpy(rep_pin[k], src, sizeof(double) * n);
-    if (sizeof(double) * n <= kZeroCopyBytes && rep_dev[k]) {
-      rep_src[k] = rep_dev[k];
+    if (in_place) {
+      rep_src[k] = rep_pin[k].dev;
       return hipSuccess;
     }
     rep_src[k] = dst;
@@ -489,10 +500,10 @@ struct gpmdm_pf {
   // frame's read-out number follows them (each event record between kernels idles the GPU
   // ~6 us; at the notebook's 0.11 ms frames that is 5%)
   hipError_t draws_used(int k, hipStream_t s) {
-    if (seq_pin && rep_dev[k] && rep_src[k] == rep_dev[k]) return hipSuccess;
-    return hipEventRecord(rep_ev[k], s);
+    if (seq_pin && rep_pin[k].dev && rep_src[k] == rep_pin[k].dev) return hipSuccess;
+    return rep_ev[k].record(s);
   }
-  int* cnt_pin = nullptr;             // class counts landing buffer (mapped; replay mode)
+  PinBuf<int> cnt_pin;                // class counts landing buffer (mapped; replay mode)
   // Host-side class counts (single small replay filters).  The per-class normals are drawn
   // on the host with shapes P_c x d after the switch, so the switch's class counts used to
   // cost a mid-frame stream synchronisation.  The switch is argmax_j T[c_p, j] / E[p, j]
@@ -501,35 +512,30 @@ struct gpmdm_pf {
   // same counts with the same fp64 divisions and comparisons while the kernels run.  The
   // device's own counts still land in cnt_pin and are compared at the next synchronisation
   // (a mismatch is an error, never a silent divergence).
-  int* cls_pin = nullptr;             // mapped: the current classes (valid when cls_host_ok)
-  int* cls_pdev = nullptr;
+  PinBuf<int> cls_pin;                // mapped: the current classes (valid when cls_host_ok)
   bool cls_host_ok = false;           // cls_pin holds the classes the next switch reads
   bool cls_ev_pending = false;        // ... once cls_ev (after the resample that wrote them) is done
-  hipEvent_t cls_ev = nullptr;
-  hipEvent_t cnt_ev = nullptr;        // after the switch whose device counts cnt_expect awaits
+  Event cls_ev;
+  Event cnt_ev;                       // after the switch whose device counts cnt_expect awaits
   std::vector<double> T_host;         // C x C
   int cnt_expect[kMaxClasses] = {0};
   bool cnt_check = false;             // compare cnt_pin with cnt_expect at the next sync
   // read-outs written by the resampling kernels straight into mapped host memory as well
   // (small read-out tables): gpmdm_pf_read then needs no copy launch, only the stream sync
-  double* ro_pin = nullptr;
-  double* ro_dev = nullptr;
-  int* cnt_dev = nullptr;
-  hipEvent_t zev[2] = {nullptr, nullptr};   // (unused: see zslot_free)
+  PinBuf<double> ro_pin;
   // A z slot is written again two frames after its frame used it; its readers (k_dyn_finish,
   // the observation tiles, the likelihood finish) precede that frame's read-out, and the
   // resample of the frame in between has recorded ro_ev by then (the call order is enforced),
   // so ro_ev guards both slots -- no event record of its own between two kernels.
   hipError_t zslot_free() {
     if (seq_pin) return wait_readout(ro_seq);
-    return ro_ev_ok ? hipEventSynchronize(ro_ev) : hipSuccess;
+    return ro_ev_ok ? ro_ev.sync() : hipSuccess;
   }
   // Filters whose read-outs land in mapped memory (one number per filter of a bank) also get
   // their sequence numbers there (the read-out kernels publish them after the values:
   // publish_readout), and the host waits on them instead of on an event recorded behind the
   // read-out -- such a record idles the GPU ~6 us before the next frame's switch.
-  long long* seq_pin = nullptr;
-  long long* seq_dev = nullptr;
+  PinBuf<long long> seq_pin;
   // the last read-out's number (0: none launched); atomic because gpmdm_pf_draws_free may
   // run on a drawing thread while the frame's thread launches the next read-out
   std::atomic<long long> ro_seq{0};
@@ -573,30 +579,27 @@ struct gpmdm_pf {
   hipError_t wait_counts() const { return wait_mapped(cseq_pin, 1, cseq, cnt_stream); }
   // the switch's class counts (replay filters): k_scan_counts publishes cseq after writing
   // them to cnt_pin, so the host's wait for them needs no event record behind the switch
-  long long* cseq_pin = nullptr;
-  long long* cseq_dev = nullptr;
+  PinBuf<long long> cseq_pin;
   long long cseq = 0;
   bool pre_counts_seq = false;        // the pending pre-switch's counts come with cseq
   int zslot = 0;
   bool z_staged = false;              // zpin[zslot] holds the frame's z, k_dyn_finish copies it
-  double *qdyn = nullptr, *mudyn = nullptr, *qobs = nullptr, *sobs = nullptr;
+  DevBuf<double> qdyn, mudyn, qobs, sobs;
   int nparts_dyn_max = 0;
   // failure detection: kHealth* counters, device, zeroed at create
-  unsigned* health = nullptr;
+  DevBuf<unsigned> health;
   // predict(): per-particle dynamics-GP means, lazily allocated
-  double *pred_q = nullptr, *pred_mu = nullptr, *pred_mu_p = nullptr, *pred_out = nullptr;
-  size_t pred_q_cap = 0;
-  double *z = nullptr, *E = nullptr, *normals = nullptr, *U = nullptr;
-  unsigned long long* gmax = nullptr;
+  DevBuf<double> pred_q, pred_mu, pred_mu_p, pred_out;
+  DevBuf<double> z, E, normals, U;
+  DevBuf<unsigned long long> gmax;
   // single filters: k_obs_ll's per-block maxima of ll, read by the normaliser in place of
   // k_norm_max (bmax_ready: produced by this frame's weigh, not yet consumed)
-  unsigned long long* bmax = nullptr;
+  DevBuf<unsigned long long> bmax;
   bool bmax_ready = false;
-  unsigned long long* bmax_rows = nullptr;   // multi-rank filters: k_rows_ll's block maxima
+  DevBuf<unsigned long long> bmax_rows;      // multi-rank filters: k_rows_ll's block maxima
   // the leader election's owner table is all 0xffffffff (the last compaction restored it)
   bool owner_clean = false;
-  double *e = nullptr, *local = nullptr, *blocksum = nullptr, *blockoffw = nullptr, *total = nullptr,
-         *partials = nullptr, *readout = nullptr;
+  DevBuf<double> e, local, blocksum, blockoffw, total, partials, readout;
   // library-driven exchange (gpmdm_pf_set_comm): an RCCL communicator of n_ranks ranks, a
   // library-owned stream for the collectives, and the packed rows.  pad = rows per rank in
   // the collective (the largest shard; ranks' shards differ by at most one row).  When the
@@ -605,20 +608,13 @@ struct gpmdm_pf {
   ncclComm_t comm = nullptr;
   bool comm_loop = false;            // comm is an in-process loopback communicator (tests)
   hipStream_t cstream = nullptr;
-  hipEvent_t cev[3] = {nullptr, nullptr, nullptr};
+  Event cev[3];
   long long pad = 0;
   bool padded = false;
-  double *xs_send = nullptr, *xs_recv = nullptr, *xs_stage = nullptr;
-  double *xl_send = nullptr, *xl_recv = nullptr, *xl_stage = nullptr;
+  DevBuf<double> xs_send, xs_recv, xs_stage, xl_send, xl_recv, xl_stage;
   void release_comm() {
     if (cstream) (void)hipStreamSynchronize(cstream);
-    double* bufs[] = {xs_send, xs_recv, xs_stage, xl_send, xl_recv, xl_stage};
-    for (double* b : bufs) dfree(b);
-    xs_send = xs_recv = xs_stage = xl_send = xl_recv = xl_stage = nullptr;
-    for (auto& e : cev) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
+    for (DevBuf<double>* b : {&xs_send, &xs_recv, &xs_stage, &xl_send, &xl_recv, &xl_stage}) b->release();
     if (cstream) (void)hipStreamDestroy(cstream);
     cstream = nullptr;
     comm = nullptr;                    // the caller owns the communicator
@@ -640,7 +636,7 @@ struct gpmdm_pf {
   // after the pre-switch: recorded on sw_stream only when another stream or the host must
   // wait for it (an event record between two kernels idles the GPU ~6 us; on the stream
   // itself the order already holds), so it covers whatever followed the pre-switch there too
-  hipEvent_t sw_ev = nullptr;
+  Event sw_ev;
   hipStream_t sw_stream = nullptr;
   // Replay filters pre-switch on the caller's request (gpmdm_pf_preswitch: the next frame's
   // Exp(1) draws are the caller's, drawn ahead on the host): the switch, its class counts into
@@ -649,14 +645,10 @@ struct gpmdm_pf {
   const double* pre_E = nullptr;
   bool pre_counts = false;            // the pre-switch's counts land in cnt_pin (cnt_done)
   hipStream_t up_stream = nullptr;    // its Exp(1) draws go up on this stream, beside the frame
-  hipEvent_t up_ev = nullptr;         // still running on the caller's (the switch waits on it)
-  hipEvent_t ndev_ev = nullptr;       // after the last dynamics finish (the device normals' reader)
+  Event up_ev;                        // still running on the caller's (the switch waits on it)
+  Event ndev_ev;                      // after the last dynamics finish (the device normals' reader)
   hipError_t make_up_stream() {
-    if (up_stream) return hipSuccess;
-    hipError_t e = hipStreamCreateWithFlags(&up_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&up_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ndev_ev, hipEventDisableTiming);
-    return e;
+    return up_stream ? hipSuccess : hipStreamCreateWithFlags(&up_stream, hipStreamNonBlocking);
   }
   // Replay normals copied to the device ahead of the propagate that reads them
   // (gpmdm_pf_stage_normals): the value ranges staged from nstage_ptr since the last propagate
@@ -672,7 +664,7 @@ struct gpmdm_pf {
     }
     return reach >= n;
   }
-  hipEvent_t ro_ev = nullptr;         // after the last read-out (gpmdm_pf_read waits on it)
+  Event ro_ev;                        // after the last read-out (gpmdm_pf_read waits on it)
   bool ro_ev_ok = false;
   int* rows_last() const { return small + 504; }   // rows of the last dynamics pass
   // Tile height of the dynamics pass on the 16 x 256 image: 16, 32 or 64 particle rows per
@@ -680,8 +672,7 @@ struct gpmdm_pf {
   // so the height is a pure schedule choice: short grids of few rows want 16-row tiles, long
   // grids 64-row ones (a B fragment feeds 4 row groups).  Chosen per frame from the row count
   // of the dynamics pass the last gpmdm_pf_read saw (k_dyn_finish writes it to rows_pin).
-  int* rows_pin = nullptr;
-  int* rows_pdev = nullptr;
+  PinBuf<int> rows_pin;
   int rows_hint = 0;
   TileGeo dyn_geo_frame{};            // this frame's dynamics launch shape (set by the switch)
   // timing
@@ -693,99 +684,23 @@ struct gpmdm_pf {
   // class tables of the step's grouping (small[0, 240)); predict() groups into its own
   // copy (small[256, 496), base 256) so the step's tables -- which gpmdm_pf_dyn_rows
   // reads -- survive a predict between steps
-  int* class_start(int base = 0) const { return small + base; }
-  int* counts(int base = 0) const { return small + base + 40; }
-  int* seg_begin(int base = 0) const { return small + base + 80; }
-  int* seg_end(int base = 0) const { return small + base + 120; }
-  int* seg_out(int base = 0) const { return small + base + 160; }
-  int* seg_tiles(int base = 0) const { return small + base + 200; }
   static constexpr int kPredictTables = 256;
-  // leader segment tables (same shape as the full ones)
-  int* lseg_begin() const { return ltab; }
-  int* lseg_end() const { return ltab + 40; }
-  int* lseg_out() const { return ltab + 80; }
-  int* lseg_tiles() const { return ltab + 120; }
-  const int* own_order() const { return own_valid ? own : nullptr; }
+  ClassTables tables(int base = 0) const { return ClassTables{small + base}; }
+  SegTables ltables() const { return SegTables{ltab}; }   // the leaders' segment tables
+  const int* own_order() const { return own_valid ? own.p : nullptr; }
 
+  // Only what has an order to respect: the side streams are drained (and destroyed) before
+  // the members' destructors, which run after this body, hand the buffers those streams used
+  // back to the pool and destroy the events; the model goes when its last user has gone.
   ~gpmdm_pf() {
     // (gpmdm_pf_destroy has waited for the filter's own work: quiesce, capi_pf.hip; a handle
     // deleted by a failed create has launched nothing)
     if (m) (void)hipSetDevice(m->device);
     if (up_stream) (void)hipStreamSynchronize(up_stream);
     release_comm();
-    double* ds[] = {T, X, X_prop, ll, qdyn, mudyn, qobs, sobs, z, E, normals, U,
-                    e, local, blocksum, blockoffw, total, partials, readout,
-                    pred_q, pred_mu, pred_mu_p, pred_out};
-    for (double* p : ds) dfree(p);
-    int* is[] = {cls, cls_new, perm, ridx, blockcounts, blockoff, small, obs_tab,
-                 slot, lflag, lblock, ltab, lperm, guide, own, own_inv, own_next, inv_next, sys_mark, sys_block};
-    for (int* p : is) dfree(p);
-    dfree(own_tmp);
-    dfree(gmax);
-    dfree(sp_stats);
-    dfree(cut_auto_dev);
-    hfree(cut_auto_host);
-    dfree(cut_part);
-    dfree(cut_split);
-    dfree(lam2_obs);
-    dfree(ro_part);
-    dfree(ro_obs);
-    hfree(ro_obs_pin);
-    if (ro_obs_ev) (void)hipEventDestroy(ro_obs_ev);
-    double* fd[] = {fc_X[0], fc_X[1], fc_q, fc_mu, fc_part, fc_ro_part, fc_out};
-    for (double* p : fd) dfree(p);
-    int* fi[] = {fc_cls[0], fc_cls[1], fc_perm, fc_blockcounts, fc_blockoff, fc_tab, fc_bcounts};
-    for (int* p : fi) dfree(p);
-    hfree(fc_pin);
-    if (fc_ev) (void)hipEventDestroy(fc_ev);
-    dfree(sm_anc);
-    dfree(sm_cls);
-    dfree(sm_X);
-    dfree(sm_part);
-    dfree(sm_out);
-    dfree(sm_ro_part);
-    dfree(sm_marks);
-    hfree(sm_pin);
-    if (sm_ev) (void)hipEventDestroy(sm_ev);
-    if (sm_tr_ev) (void)hipEventDestroy(sm_tr_ev);
-    dfree(vc_prop);
-    dfree(iv_part);
-    dfree(iv_out);
-    hfree(iv_pin);
-    hfree(pv_mask);
-    if (iv_ev) (void)hipEventDestroy(iv_ev);
-    double* gd[] = {gt_part, gt_out, gt_tab, gt_sp, gt_lil};
-    for (double* p : gd) dfree(p);
-    hfree(gt_pin);
-    dfree(bmax);
-    dfree(bmax_rows);
-    dfree(owner);
-    dfree(health);
+    if (up_stream) (void)hipStreamDestroy(up_stream);
     for (auto& r : recs) { pool.push_back(r.a); pool.push_back(r.b); }
     for (auto ev : pool) (void)hipEventDestroy(ev);
-    hfree(rpin);
-    hfree(cnt_pin);
-    hfree(cseq_pin);
-    hfree(rows_pin);
-    hfree(cls_pin);
-    if (cls_ev) (void)hipEventDestroy(cls_ev);
-    if (cnt_ev) (void)hipEventDestroy(cnt_ev);
-    if (sw_ev) (void)hipEventDestroy(sw_ev);
-    if (ro_ev) (void)hipEventDestroy(ro_ev);
-    if (cnt_done) (void)hipEventDestroy(cnt_done);
-    if (up_ev) (void)hipEventDestroy(up_ev);
-    if (ndev_ev) (void)hipEventDestroy(ndev_ev);
-    if (up_stream) (void)hipStreamDestroy(up_stream);
-    hfree(ro_pin);
-    hfree(seq_pin);
-    for (int k = 0; k < 2; ++k) {
-      hfree(zpin[k]);
-      if (zev[k]) (void)hipEventDestroy(zev[k]);
-    }
-    for (int k = 0; k < 3; ++k) {
-      hfree(rep_pin[k]);
-      if (rep_ev[k]) (void)hipEventDestroy(rep_ev[k]);
-    }
     if (m) m->remove_user(this);
     model_release(m);
   }
@@ -825,19 +740,20 @@ int quiesce_users(gpmdm_model* m);
 int sm_wait(gpmdm_pf* pf);
 int sm_record(gpmdm_pf* pf, hipStream_t s);
 int sm_clear(gpmdm_pf* pf, hipStream_t s);
-// the forecast's class tables (fc_tab): the layout of gpmdm_pf::small's (class_start, counts, segments)
-struct FcTables {
-  int* t;
-  int* class_start() const { return t; }
-  int* counts() const { return t + 40; }
-  int* seg_begin() const { return t + 80; }
-  int* seg_end() const { return t + 120; }
-  int* seg_out() const { return t + 160; }
-  int* seg_tiles() const { return t + 200; }
-};
 // the pose read-out over the F clouds at X (F x Pf x d) into out (F x {mean[D], spread[D]});
-// capi_forecast.hip
-ReadoutParams rollout_readout(const gpmdm_pf* pf, const double* X, double* part, double* out);
+// capi_pf.hip
+ReadoutParams pose_readout(const gpmdm_pf* pf, const double* X, double* part, double* out);
+// The common part of the class grouping's two launches (launch_scan_counts, launch_group) over
+// all P particles with classes `cls`, whose per-block counts are in blockcounts: tables, block
+// offsets and the permutation it writes; pt: the tile unit of the dynamics pass.  capi_pf.hip
+void fill_grouping(ScanArgs& sc, GroupArgs& ga, ClassTables tb, const int* blockcounts, int* blockoff, int* perm,
+                   const int* cls, long long P, int C, int pt);
+// The dynamics-GP tile launches of image set dset in shape geo (per class, segments of at most
+// kMaxSeg classes per launch) over the rows of X that tb and perm name, at most rows_ub of
+// them, into q (leading dimension ld_q) and mu.  capi_frame.hip
+void launch_dyn_tiles(const gpmdm_model* m, const std::vector<GpImage>& dset, TileGeo geo, SegTables tb,
+                      const int* perm, const double* X, long long rows_ub, double* q, long long ld_q, double* mu,
+                      hipStream_t s);
 int sm_set(gpmdm_pf* pf, int lag);     // (set_smoothing of a checked handle, single or bank)
 int iv_wait(gpmdm_pf* pf);             // an innovation call's launches in flight (capi_innov.hip)
 // gating (capi_gate.hip): the end of a gated-mode weigh on s; the log il2 table of the filter's
@@ -848,16 +764,6 @@ int gate_rebind(gpmdm_pf* pf);
 // doubles); so may the smoothing ring, and a smoothed read-out's staging of the particle rows
 constexpr size_t kForecastStageBytes = (size_t)1 << 30;
 constexpr size_t kSmoothBytes = (size_t)1 << 30;
-// a read-out's scratch grown inside a call: the old buffer is released after s's earlier work
-template <typename T>
-int grow(T*& p, size_t& cap, size_t n, hipStream_t s) {
-  if (cap >= n) return GPMDM_OK;
-  dfree_after(p, s);
-  cap = 0;
-  TRY(dalloc(&p, n));
-  cap = n;
-  return GPMDM_OK;
-}
 int h2d(void* dst, const void* src, size_t bytes);
 // the observation-GP cutoff image (capi_model.hip; packed on the host or the device)
 struct CutoffPlan {

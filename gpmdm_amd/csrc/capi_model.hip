@@ -2,6 +2,8 @@
 // per-class dynamics GPs, host_image.h) and the predictive maps gpmdm_predict_obs / dyn
 // (map_x_to_y, gpmdm.py:923-963; map_x_dynamics_for_class, gpmdm.py:1032-1068); the
 // thread-local last error.
+#include <memory>
+
 #include "capi_internal.h"
 
 namespace gpmdm {
@@ -29,9 +31,9 @@ int h2d(void* dst, const void* src, size_t bytes) {
 }
 
 template <typename T>
-int upload(T** dst, const std::vector<T>& v) {
-  TRY(dalloc(dst, v.size()));
-  return h2d(*dst, v.data(), v.size() * sizeof(T));
+int upload(DevBuf<T>& dst, const std::vector<T>& v) {
+  TRY(dst.alloc(v.size()));
+  return h2d(dst, v.data(), v.size() * sizeof(T));
 }
 
 // Wait for the last frame of every filter built on the model (not for the device): the
@@ -58,12 +60,12 @@ int build_image(GpImage& g, int n_rows, int d, int n_m, const double* X, const d
   g.n_j = pk.n_j;
   std::vector<double> rec, hf;
   pk.records(rec);
-  TRY(upload(&g.Xrec, rec));
+  TRY(upload(g.Xrec, rec));
   if (lin_c2) {
     pk.linear(hf);
-    TRY(upload(&g.Hf, hf));
+    TRY(upload(g.Hf, hf));
   }
-  TRY(dalloc(&g.Bf, (size_t)pk.total_doubles()));
+  TRY(g.Bf.alloc((size_t)pk.total_doubles()));
   long long off = 0;
   std::vector<double> buf;
   for (int J = 0; J < g.n_j; ++J) {
@@ -104,10 +106,10 @@ int cutoff_install(gpmdm_model* m, const CutoffPlan& pl, const std::function<int
   TRY(quiesce_users(m));              // the filters' own launches may still read the old image
   m->release_cutoff();
   auto& ci = m->obs_cut;
-  int rc = upload(&ci.sph, pl.sph);
-  if (!rc) rc = upload(&ci.Xrec, pl.rec);
-  if (!rc) rc = upload(&ci.toff, pl.toff);
-  if (!rc) rc = dalloc(&ci.Bt, (size_t)pl.toff.back());
+  int rc = upload(ci.sph, pl.sph);
+  if (!rc) rc = upload(ci.Xrec, pl.rec);
+  if (!rc) rc = upload(ci.toff, pl.toff);
+  if (!rc) rc = ci.Bt.alloc((size_t)pl.toff.back());
   if (!rc) rc = fill(ci.Bt, ci.toff);
   if (rc) {
     m->release_cutoff();
@@ -171,7 +173,8 @@ int gpmdm_model_create(const gpmdm_model_desc* desc, int device, gpmdm_model_t* 
     CHECK(why.empty(), why);
   }
   HIPCHK(hipSetDevice(device));
-  auto* m = new gpmdm_model();
+  std::unique_ptr<gpmdm_model> holder(new gpmdm_model());   // released on every failure below
+  gpmdm_model* m = holder.get();
   m->device = device;
   m->N = desc->N;
   m->D = desc->D;
@@ -208,14 +211,14 @@ int gpmdm_model_create(const gpmdm_model_desc* desc, int device, gpmdm_model_t* 
   }
   int rc = build_image(m->obs, (int)m->N, d, m->D, desc->X, desc->y_lengthscales, nullptr,
                        desc->obs_R, desc->obs_beta, obs_geo);
-  if (rc) { delete m; return rc; }
+  TRY(rc);
   {
     const char* e = std::getenv("GPMDM_OBS_IMAGE16");       // "0": not built (A/B, tests)
     if (m->N <= kSmallObsN && d <= 12 && obs_geo.nw == kGeo32x512.nw && obs_geo.mt == kGeo32x512.mt &&
         obs_geo.ntw == kGeo32x512.ntw && !(e && e[0] == '0')) {
       rc = build_image(m->obs_small, (int)m->N, d, m->D, desc->X, desc->y_lengthscales, nullptr,
                        desc->obs_R, desc->obs_beta, kGeo16x256);
-      if (rc) { delete m; return rc; }
+      TRY(rc);
     }
   }
   m->dyn.resize(m->C);
@@ -225,41 +228,34 @@ int gpmdm_model_create(const gpmdm_model_desc* desc, int device, gpmdm_model_t* 
     rc = build_image(m->dyn[c], (int)desc->Nc[c], d, d, desc->Xin[c], desc->x_lengthscales,
                      m->x_lin_c2.data(),
                      desc->dyn_R[c], desc->dyn_alpha[c], dyn_geo);
-    if (rc) { delete m; return rc; }
+    TRY(rc);
     if (two) {
       rc = build_image(m->dynw[c], (int)desc->Nc[c], d, d, desc->Xin[c], desc->x_lengthscales,
                        m->x_lin_c2.data(), desc->dyn_R[c], desc->dyn_alpha[c], dynw_geo);
-      if (rc) { delete m; return rc; }
+      TRY(rc);
     }
   }
-  rc = dalloc(&m->y_il2_dev, m->D);
-  if (rc) { delete m; return rc; }
-  if (h2d(m->y_il2_dev, m->y_il2.data(), m->D * sizeof(double)) != GPMDM_OK) {
-    delete m;
+  TRY(m->y_il2_dev.alloc(m->D));
+  if (h2d(m->y_il2_dev, m->y_il2.data(), m->D * sizeof(double)) != GPMDM_OK)
     return fail(GPMDM_E_HIP, "upload y_inv_lambda2");
-  }
   {
     std::vector<double> lam2(m->D);
     for (int j = 0; j < m->D; ++j) {
       lam2[j] = 1.0 / m->y_il2[j];
       m->sum_log_il2 += std::log(m->y_il2[j]);
     }
-    rc = dalloc(&m->y_lam2_dev, m->D);
-    if (rc) { delete m; return rc; }
-    if (h2d(m->y_lam2_dev, lam2.data(), m->D * sizeof(double)) != GPMDM_OK) {
-      delete m;
+    TRY(m->y_lam2_dev.alloc(m->D));
+    if (h2d(m->y_lam2_dev, lam2.data(), m->D * sizeof(double)) != GPMDM_OK)
       return fail(GPMDM_E_HIP, "upload lambda^2");
-    }
   }
   {
     // the filtered-pose read-out's operands (obs_readout.h)
     std::vector<double> bro;
     pack_readout_beta(desc->obs_beta, m->N, m->D, bro);
-    rc = upload(&m->ro_beta, bro);
-    if (!rc) rc = upload(&m->y_ls_dev, m->y_ls);
-    if (rc) { delete m; return rc; }
+    TRY(upload(m->ro_beta, bro));
+    TRY(upload(m->y_ls_dev, m->y_ls));
   }
-  *out = m;
+  *out = holder.release();
   return GPMDM_OK;
 }
 

@@ -2,9 +2,25 @@
 // particle state (gpmdm_pf.py:78-115), settings (de-duplication, tile images, shard order,
 // model rebind, timing), health counters and predict().  The banks are filters with F > 1
 // (gpmdm_bank_create): every entry point here serves both.
+#include <memory>
+
 #include "capi_internal.h"
 
 namespace gpmdm::capi {
+
+// The ownership order's buffers (shard_order.hip): multi-rank Philox filters at create,
+// single-rank ones with the observation-GP cutoff.  All or none.
+static int alloc_order(gpmdm_pf* pf) {
+  const size_t P = (size_t)pf->P;
+  pf->own_tmp_bytes = std::max<size_t>(uniform_order_temp_bytes(pf->P), 1);
+  if (pf->own.alloc(P) || pf->own_inv.alloc(P) || pf->own_next.alloc(P) || pf->inv_next.alloc(P) ||
+      pf->own_tmp.alloc(pf->own_tmp_bytes)) {
+    for (DevBuf<int>* b : {&pf->own, &pf->own_inv, &pf->own_next, &pf->inv_next}) b->release();
+    pf->own_tmp.release();
+    return fail(GPMDM_E_NOMEM, "ownership order buffers");
+  }
+  return GPMDM_OK;
+}
 
 // ------------------------------------------------------------------------------------
 static int pf_create(gpmdm_model_t m, const double* T, int64_t F, int64_t Pf, int rng_mode, uint64_t seed,
@@ -20,7 +36,8 @@ static int pf_create(gpmdm_model_t m, const double* T, int64_t F, int64_t Pf, in
         "bad resample mode");
   CHECK(n_ranks >= 1 && rank >= 0 && rank < n_ranks, "bad rank");
   HIPCHK(hipSetDevice(m->device));
-  auto* pf = new gpmdm_pf();
+  std::unique_ptr<gpmdm_pf> holder(new gpmdm_pf());   // released on every failure below
+  gpmdm_pf* pf = holder.get();
   pf->m = m;
   m->refs.fetch_add(1);   // released by ~gpmdm_pf
   pf->P = P;
@@ -41,8 +58,7 @@ static int pf_create(gpmdm_model_t m, const double* T, int64_t F, int64_t Pf, in
   const int maxparts = m->dyn_parts_max();
   pf->nparts_dyn_max = maxparts;
   const long long nl = std::max(pf->nloc, 1ll);
-  int rc = 0;
-#define ALLOC(ptr, n) do { rc = dalloc(&pf->ptr, (size_t)(n)); if (rc) { delete pf; return rc; } } while (0)
+#define ALLOC(buf, n) TRY(pf->buf.alloc((size_t)(n)))
   ALLOC(T, C * C);
   ALLOC(X, P * d);
   ALLOC(X_prop, P * d);
@@ -87,106 +103,30 @@ static int pf_create(gpmdm_model_t m, const double* T, int64_t F, int64_t Pf, in
     ALLOC(sys_mark, P);
     ALLOC(sys_block, F * pf->nbf);
   }
-  if (n_ranks > 1 && rng_mode == GPMDM_RNG_PHILOX) {
-    pf->own_tmp_bytes = std::max<size_t>(uniform_order_temp_bytes(P), 1);
-    ALLOC(own, P);
-    ALLOC(own_inv, P);
-    ALLOC(own_next, P);
-    ALLOC(inv_next, P);
-    ALLOC(own_tmp, pf->own_tmp_bytes);
-  }
+  if (n_ranks > 1 && rng_mode == GPMDM_RNG_PHILOX) TRY(alloc_order(pf));
 #undef ALLOC
-  for (int k = 0; k < 2; ++k) {
-    void* zv = nullptr;
-    if (halloc(&pf->zpin[k], (size_t)(F * D), hipHostMallocMapped | hipHostMallocCoherent) != GPMDM_OK ||
-        hipEventCreateWithFlags(&pf->zev[k], hipEventDisableTiming) != hipSuccess ||
-        hipHostGetDevicePointer(&zv, pf->zpin[k], 0) != hipSuccess) {
-      delete pf;
-      return fail(GPMDM_E_NOMEM, "pinned observation buffer");
-    }
-    pf->zdev[k] = (const double*)zv;
-  }
-  if (halloc(&pf->rpin, (size_t)(F * (C + d + 1)), 0) != GPMDM_OK) {
-    delete pf;
-    return fail(GPMDM_E_NOMEM, "pinned read-out buffer");
-  }
+  for (int k = 0; k < 2; ++k)
+    if (pf->zpin[k].alloc_mapped((size_t)(F * D))) return fail(GPMDM_E_NOMEM, "pinned observation buffer");
+  if (pf->rpin.alloc((size_t)(F * (C + d + 1)))) return fail(GPMDM_E_NOMEM, "pinned read-out buffer");
   if (sizeof(double) * F * (C + d + 1) <= 32768) {
-    void* rv = nullptr;
-    if (halloc(&pf->ro_pin, (size_t)(F * (C + d + 1)), hipHostMallocMapped | hipHostMallocCoherent) != GPMDM_OK ||
-        hipHostGetDevicePointer(&rv, pf->ro_pin, 0) != hipSuccess) {
-      delete pf;
-      return fail(GPMDM_E_NOMEM, "mapped read-out buffer");
-    }
-    pf->ro_dev = (double*)rv;
-    void* sv = nullptr;
-    if (halloc(&pf->seq_pin, (size_t)(F), hipHostMallocMapped | hipHostMallocCoherent) != GPMDM_OK ||
-        hipHostGetDevicePointer(&sv, pf->seq_pin, 0) != hipSuccess) {
-      delete pf;
-      return fail(GPMDM_E_NOMEM, "mapped read-out number");
-    }
+    if (pf->ro_pin.alloc_mapped((size_t)(F * (C + d + 1)))) return fail(GPMDM_E_NOMEM, "mapped read-out buffer");
+    if (pf->seq_pin.alloc_mapped((size_t)F)) return fail(GPMDM_E_NOMEM, "mapped read-out number");
     for (long long f = 0; f < F; ++f) pf->seq_pin[f] = 0;
-    pf->seq_dev = (long long*)sv;
   }
-  {
-    void* rv = nullptr;
-    if (halloc(&pf->rows_pin, 1, hipHostMallocMapped | hipHostMallocCoherent) != GPMDM_OK ||
-        hipHostGetDevicePointer(&rv, pf->rows_pin, 0) != hipSuccess) {
-      delete pf;
-      return fail(GPMDM_E_NOMEM, "mapped row-count buffer");
-    }
-    pf->rows_pdev = (int*)rv;
-    *pf->rows_pin = 0;
-  }
+  if (pf->rows_pin.alloc_mapped(1)) return fail(GPMDM_E_NOMEM, "mapped row-count buffer");
+  *pf->rows_pin = 0;
   if (rng_mode == GPMDM_RNG_REPLAY) {
     const long long n[3] = {P * C, P * d, P};      // E, normals, U
     // mapped, coherent (fine-grained): kernels may read the small draws in place
-    const unsigned fl = hipHostMallocMapped | hipHostMallocCoherent;
-    for (int k = 0; k < 3; ++k) {
-      void* dv = nullptr;
-      if (halloc(&pf->rep_pin[k], (size_t)(n[k]), fl) != GPMDM_OK ||
-          hipEventCreateWithFlags(&pf->rep_ev[k], hipEventDisableTiming) != hipSuccess ||
-          hipHostGetDevicePointer(&dv, pf->rep_pin[k], 0) != hipSuccess) {
-        delete pf;
-        return fail(GPMDM_E_NOMEM, "pinned replay-draw buffer");
-      }
-      pf->rep_dev[k] = (const double*)dv;
-    }
-    void* cv = nullptr;
-    if (halloc(&pf->cnt_pin, (size_t)(kMaxClasses), fl) != GPMDM_OK ||
-        hipHostGetDevicePointer(&cv, pf->cnt_pin, 0) != hipSuccess) {
-      delete pf;
-      return fail(GPMDM_E_NOMEM, "pinned class-count buffer");
-    }
-    pf->cnt_dev = (int*)cv;
-    void* qv = nullptr;
-    if (halloc(&pf->cseq_pin, 1, fl) != GPMDM_OK ||
-        hipHostGetDevicePointer(&qv, pf->cseq_pin, 0) != hipSuccess) {
-      delete pf;
-      return fail(GPMDM_E_NOMEM, "mapped class-count number");
-    }
+    for (int k = 0; k < 3; ++k)
+      if (pf->rep_pin[k].alloc_mapped((size_t)(n[k]))) return fail(GPMDM_E_NOMEM, "pinned replay-draw buffer");
+    if (pf->cnt_pin.alloc_mapped((size_t)(kMaxClasses))) return fail(GPMDM_E_NOMEM, "pinned class-count buffer");
+    if (pf->cseq_pin.alloc_mapped(1)) return fail(GPMDM_E_NOMEM, "mapped class-count number");
     *pf->cseq_pin = 0;
-    pf->cseq_dev = (long long*)qv;
     if (F == 1 && n_ranks == 1 && P <= kHostCountsMaxP) {
-      void* lv = nullptr;
-      if (halloc(&pf->cls_pin, (size_t)(P), fl) != GPMDM_OK ||
-          hipHostGetDevicePointer(&lv, pf->cls_pin, 0) != hipSuccess ||
-          hipEventCreateWithFlags(&pf->cls_ev, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&pf->cnt_ev, hipEventDisableTiming) != hipSuccess) {
-        delete pf;
-        return fail(GPMDM_E_NOMEM, "pinned class buffer");
-      }
-      pf->cls_pdev = (int*)lv;
+      if (pf->cls_pin.alloc_mapped((size_t)(P))) return fail(GPMDM_E_NOMEM, "pinned class buffer");
       pf->T_host.assign(T, T + (size_t)C * C);
     }
-  }
-  if (rng_mode == GPMDM_RNG_REPLAY && hipEventCreateWithFlags(&pf->cnt_done, hipEventDisableTiming) != hipSuccess) {
-    delete pf;
-    return fail(GPMDM_E_HIP, "filter events");
-  }
-  if (hipEventCreateWithFlags(&pf->sw_ev, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&pf->ro_ev, hipEventDisableTiming) != hipSuccess) {
-    delete pf;
-    return fail(GPMDM_E_HIP, "filter events");
   }
   pf->preswitch = rng_mode == GPMDM_RNG_PHILOX && std::getenv("GPMDM_NO_PRESWITCH") == nullptr;
   pf->obs_img = &obs_pick(m, pf->Pf, pf->nloc, pf->obs_geo);
@@ -195,12 +135,10 @@ static int pf_create(gpmdm_model_t m, const double* T, int64_t F, int64_t Pf, in
   if (!life || hipMemcpyAsync(pf->obs_tab, tab, sizeof(tab), hipMemcpyHostToDevice, life) != hipSuccess ||
       hipMemcpyAsync(pf->T, T, sizeof(double) * C * C, hipMemcpyHostToDevice, life) != hipSuccess ||
       hipMemsetAsync(pf->health, 0, sizeof(unsigned) * kHealthN, life) != hipSuccess ||
-      hipMemsetAsync(pf->small, 0, sizeof(int) * 512, life) != hipSuccess || hipStreamSynchronize(life) != hipSuccess) {
-    delete pf;
+      hipMemsetAsync(pf->small, 0, sizeof(int) * 512, life) != hipSuccess || hipStreamSynchronize(life) != hipSuccess)
     return fail(GPMDM_E_HIP, "upload of particle-filter tables failed");
-  }
   m->add_user(pf);
-  *out = pf;
+  *out = holder.release();
   return GPMDM_OK;
 }
 
@@ -229,7 +167,7 @@ ResampleArgs resample_args(gpmdm_pf* pf) {
   ra.ridx = pf->ridx;
   ra.partials = pf->partials;
   ra.readout = pf->readout;
-  ra.readout_host = pf->ro_dev;
+  ra.readout_host = pf->ro_pin.dev;
   ra.guide = pf->guide;
   ra.GB = guide_buckets_used(pf->Pf);   // 0: plain search
   ra.sys_mark = pf->sys_mark;           // systematic: by scan, no search
@@ -270,11 +208,11 @@ int flush_ll(gpmdm_pf* pf, hipStream_t s) {
 // the next gpmdm_pf_switch launches the switch again (same draws: the same tables).
 int drop_preswitch(gpmdm_pf* pf, hipStream_t s, bool host_wait) {
   if (!pf->preswitched) return GPMDM_OK;
-  if (host_wait || s != pf->sw_stream) HIPCHK(hipEventRecord(pf->sw_ev, pf->sw_stream));   // (see sw_ev)
+  if (host_wait || s != pf->sw_stream) HIPCHK(pf->sw_ev.record(pf->sw_stream));   // (see sw_ev)
   if (host_wait)
-    HIPCHK(hipEventSynchronize(pf->sw_ev));
+    HIPCHK(pf->sw_ev.sync());
   else if (s != pf->sw_stream)
-    HIPCHK(hipStreamWaitEvent(s, pf->sw_ev, 0));
+    HIPCHK(pf->sw_ev.block(s));
   pf->preswitched = false;
   pf->switched = false;
   pf->gemm_ahead = pf->pre_counts = false;   // (a replay pre-switch's tiles are redone too)
@@ -296,23 +234,16 @@ int quiesce(gpmdm_pf* pf) {
   } else if (pf->seq_pin && pf->ro_seq.load() > 0) {
     HIPCHK(pf->wait_readout(pf->ro_seq.load()));
   } else if (pf->ro_ev_ok) {
-    HIPCHK(hipEventSynchronize(pf->ro_ev));
+    HIPCHK(pf->ro_ev.sync());
   }
   if (pf->up_stream) HIPCHK(hipStreamSynchronize(pf->up_stream));
   if (pf->cstream) HIPCHK(hipStreamSynchronize(pf->cstream));
-  if (pf->ro_obs_pending) {            // a filtered-pose read-out launched without a copy
-    HIPCHK(hipEventSynchronize(pf->ro_obs_ev));
-    pf->ro_obs_pending = false;
-  }
-  if (pf->fc_pending) {                // a forecast that failed before its own wait
-    HIPCHK(hipEventSynchronize(pf->fc_ev));
-    pf->fc_pending = false;
-  }
-  // a smoothing record follows the frame's read-out number on the frame's stream; a smoothed
-  // read-out that failed before its own wait
+  // read-outs launched without a copy, or that failed before their own wait (Landing::wait);
+  // a smoothing record follows the frame's read-out number on the frame's stream
+  TRY(pf->ro_obs.wait());
+  TRY(pf->fc_out.wait());
   TRY(sm_wait(pf));
-  TRY(iv_wait(pf));                    // an innovation call that failed before its own wait
-  return GPMDM_OK;
+  return iv_wait(pf);
 }
 
 // The mask's device array and scalars from the filter's current model (gpmdm_pf_set_obs_mask,
@@ -326,7 +257,7 @@ static int install_obs_mask(gpmdm_pf* pf, const std::vector<unsigned char>& mask
   // F rows of lam2 (a bank: one mask per filter), then the finish's F-row table of scalars
   const int F = pf->F;
   const size_t n_lam = (size_t)F * D, n_all = n_lam + 3 * (size_t)F;
-  if (!pf->lam2_obs) TRY(dalloc(&pf->lam2_obs, n_all));
+  if (!pf->lam2_obs) TRY(pf->lam2_obs.alloc(n_all));
   std::vector<double> lam2(n_all, 0.0);
   int n_tot = 0;
   double sl = 0.0, lc = 0.0;
@@ -340,7 +271,7 @@ static int install_obs_mask(gpmdm_pf* pf, const std::vector<unsigned char>& mask
         sl += std::log(m->y_il2[(size_t)j]);
         ++n_obs;
       }
-    lc = (double)((float)(0.5 * n_obs) * (float)1.8378770351409912);   // capi_frame.hip weigh()
+    lc = ll_const(n_obs);
     double* row = lam2.data() + n_lam + 3 * (size_t)f;
     row[0] = (double)n_obs;
     row[1] = sl;
@@ -353,6 +284,50 @@ static int install_obs_mask(gpmdm_pf* pf, const std::vector<unsigned char>& mask
   pf->sum_log_il2_obs = sl;            // (single filters: the finish's arguments)
   pf->ll_const_obs = lc;
   return GPMDM_OK;
+}
+
+ReadoutParams pose_readout(const gpmdm_pf* pf, const double* X, double* part, double* out) {
+  const gpmdm_model* m = pf->m;
+  ReadoutParams rp{};
+  rp.X = X;
+  rp.P = pf->Pf;
+  rp.F = pf->F;
+  rp.d = m->d;
+  rp.D = m->D;
+  rp.ls = m->y_ls_dev;
+  rp.Xrec = m->obs.Xrec;
+  rp.nks = ksteps((int)m->N);
+  rp.Bro = m->ro_beta;
+  rp.n_groups = readout_groups(m->D);
+  rp.part = part;
+  rp.out = out;
+  return rp;
+}
+
+void fill_grouping(ScanArgs& sc, GroupArgs& ga, ClassTables tb, const int* blockcounts, int* blockoff, int* perm,
+                   const int* cls, long long P, int C, int pt) {
+  const SegTables sg = tb.seg();
+  sc.nb = (int)cdiv(P, 256);
+  sc.C = C;
+  sc.pt = pt;
+  sc.lo = 0;
+  sc.hi = P;
+  sc.blockcounts = blockcounts;
+  sc.cls_new = cls;
+  sc.blockoff = blockoff;
+  sc.class_start = tb.class_start();
+  sc.counts = tb.counts();
+  sc.seg_pos_begin = sg.begin();
+  sc.seg_pos_end = sg.end();
+  sc.seg_out_base = sg.out();
+  sc.seg_tile_start = sg.tiles();
+  ga.P = P;
+  ga.n = P;
+  ga.C = C;
+  ga.cls_new = cls;
+  ga.class_start = tb.class_start();
+  ga.blockoff = blockoff;
+  ga.perm = perm;
 }
 
 }  // namespace gpmdm::capi
@@ -400,7 +375,7 @@ int gpmdm_pf_init(gpmdm_pf_t pf, const double* states, const int64_t* classes) {
   CHECK(ls, "the library's lifecycle stream");
   std::vector<int> r32(P);
   for (long long i = 0; i < P; ++i) r32[i] = (int)(i % pf->Pf);   // no shared ancestors yet
-  const std::vector<unsigned long long> neg(pf->F, 0x000fffffffffffffull);   // ord_enc(-inf)
+  const std::vector<unsigned long long> neg(pf->F, host_ord_enc(-INFINITY));
   HIPCHK(hipMemcpyAsync(pf->X, states, sizeof(double) * P * m->d, hipMemcpyHostToDevice, ls));
   HIPCHK(hipMemcpyAsync(pf->cls, c32.data(), sizeof(int) * P, hipMemcpyHostToDevice, ls));
   HIPCHK(hipMemcpyAsync(pf->ridx, r32.data(), sizeof(int) * P, hipMemcpyHostToDevice, ls));
@@ -418,7 +393,7 @@ int gpmdm_pf_init(gpmdm_pf_t pf, const double* states, const int64_t* classes) {
   ra.X_src = pf->X;
   launch_normalise_resample(norm_args(pf), ra, ls);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(pf->ro_ev, ls));
+  HIPCHK(pf->ro_ev.record(ls));
   HIPCHK(hipStreamSynchronize(ls));
   pf->ro_ev_ok = true;
   if (pf->seq_pin) pf->ro_seq = pf->seq_min();   // (synchronised: nothing to wait for)
@@ -464,9 +439,7 @@ int gpmdm_pf_import(gpmdm_pf_t pf, const double* states, const int64_t* classes,
       CHECK(std::memcmp(&lw, &log_w[i], sizeof(double)) == 0 || (std::isnan(lw) && std::isnan(log_w[i])),
             "log_w is not ll - max(ll) of its filter");
     }
-    unsigned long long u;
-    std::memcpy(&u, &M, sizeof(u));
-    gm[f] = (u >> 63) ? ~u : (u | 0x8000000000000000ull);   // ord_enc (common.h)
+    gm[f] = host_ord_enc(M);
   }
   const std::vector<double> ones(F, 1.0);
   hipStream_t ls = life_stream(m->device);   // uploads and read-outs on the lifecycle stream
@@ -497,7 +470,7 @@ int gpmdm_pf_import(gpmdm_pf_t pf, const double* states, const int64_t* classes,
   // state; the ownership order changes which rank evaluates a particle, never its values)
   pf->own_valid = false;
   pf->rows_st = pf->rows_ll = nullptr;
-  HIPCHK(hipEventRecord(pf->ro_ev, ls));
+  HIPCHK(pf->ro_ev.record(ls));
   HIPCHK(hipStreamSynchronize(ls));
   pf->ro_ev_ok = true;
   if (pf->seq_pin) pf->ro_seq = pf->seq_min();   // (synchronised: nothing to wait for)
@@ -533,9 +506,7 @@ int gpmdm_pf_export(gpmdm_pf_t pf, double* states, int64_t* classes, double* ll,
   for (long long i = 0; i < (ridx ? P : 0); ++i) ridx[i] = tr[i];
   if (ll) std::memcpy(ll, l.data(), sizeof(double) * P);
   for (int f = 0; f < pf->F; ++f) {
-    const unsigned long long v = (gm[f] >> 63) ? (gm[f] & 0x7fffffffffffffffull) : ~gm[f];
-    double M;
-    std::memcpy(&M, &v, sizeof(M));
+    const double M = host_ord_dec(gm[f]);
     for (long long i = f * pf->Pf; i < (f + 1) * pf->Pf; ++i) {
       if (log_w) log_w[i] = l[i] - M;
       if (w) w[i] /= S[f];
@@ -633,40 +604,25 @@ int gpmdm_pf_set_model(gpmdm_pf_t pf, gpmdm_model_t m) {
   // buffers shaped by the model's column blocks
   const int maxparts = m->dyn_parts_max();
   const long long nl = std::max(pf->nloc, 1ll);
-  double *qdyn = nullptr, *qobs = nullptr, *sobs = nullptr;
-  int rc = dalloc(&qdyn, (size_t)maxparts * nl);
-  if (!rc) rc = dalloc(&qobs, (size_t)obs_parts_max(m) * nl);
-  if (!rc) rc = dalloc(&sobs, (size_t)obs_blocks_max(m) * nl);
+  DevBuf<double> qdyn, qobs, sobs;     // (released on every failure below)
+  TRY(qdyn.alloc((size_t)maxparts * nl));
+  TRY(qobs.alloc((size_t)obs_parts_max(m) * nl));
+  TRY(sobs.alloc((size_t)obs_blocks_max(m) * nl));
   TileGeo og{};
   const GpImage* oimg = &obs_pick(m, pf->Pf, pf->nloc, og);
-  if (rc) {
-    dfree(qdyn);
-    dfree(qobs);
-    dfree(sobs);
-    return rc;
-  }
   // the filter's own launches in flight may still read the old buffers and obs_tab: wait for
   // them (not for the device), then release the old buffers in the lifecycle stream's order
   TRY(quiesce(pf));
   const int tab[5] = {(int)pf->lo, (int)pf->hi, 0, 0, (int)cdiv(pf->nloc, og.pt())};
   hipStream_t ls = life_stream(m->device);
   if (!ls || hipMemcpyAsync(pf->obs_tab, tab, sizeof(tab), hipMemcpyHostToDevice, ls) != hipSuccess ||
-      hipStreamSynchronize(ls) != hipSuccess) {
-    dfree(qdyn);
-    dfree(qobs);
-    dfree(sobs);
+      hipStreamSynchronize(ls) != hipSuccess)
     return fail(GPMDM_E_HIP, "upload of the observation tile table");
-  }
-  dfree(pf->qdyn);
-  dfree(pf->qobs);
-  dfree(pf->sobs);
-  dfree(pf->pred_q);
-  pf->pred_q_cap = 0;
-  dfree(pf->fc_q);                     // (the forecast's tile partials: as predict's)
-  pf->fc_q_cap = 0;
-  pf->qdyn = qdyn;
-  pf->qobs = qobs;
-  pf->sobs = sobs;
+  pf->qdyn = std::move(qdyn);
+  pf->qobs = std::move(qobs);
+  pf->sobs = std::move(sobs);
+  pf->pred_q.release();
+  pf->fc_q.release();                  // (the forecast's tile partials: as predict's)
   pf->nparts_dyn_max = maxparts;
   pf->obs_geo = og;
   pf->obs_img = oimg;
@@ -694,29 +650,17 @@ int gpmdm_pf_set_obs_cutoff(gpmdm_pf_t pf, int mode) {
   if (mode && !pf->own && pf->rng_mode == GPMDM_RNG_PHILOX && pf->F == 1 && uniform_order_supported(pf->P)) {
     // the ownership order for single-rank filters (order_wanted): resampling-ancestor ranges
     // of particles evaluated together, so the cutoff's particle tiles are compact
-    pf->own_tmp_bytes = std::max<size_t>(uniform_order_temp_bytes(pf->P), 1);
-    if (dalloc(&pf->own, (size_t)pf->P) || dalloc(&pf->own_inv, (size_t)pf->P) || dalloc(&pf->own_next, (size_t)pf->P) ||
-        dalloc(&pf->inv_next, (size_t)pf->P) || dalloc(&pf->own_tmp, pf->own_tmp_bytes)) {
-      dfree(pf->own);
-      dfree(pf->own_inv);
-      dfree(pf->own_next);
-      dfree(pf->inv_next);
-      dfree(pf->own_tmp);
-      return fail(GPMDM_E_NOMEM, "ownership order buffers");
-    }
+    TRY(alloc_order(pf));
   }
   if (!mode && pf->n_ranks == 1) pf->own_valid = false;   // (the order is the cutoff's only)
   if (mode == 2 && !pf->sp_stats) {
-    TRY(dalloc(&pf->sp_stats, 2));
+    TRY(pf->sp_stats.alloc(2));
     HIPCHK(hipMemset(pf->sp_stats, 0, 2 * sizeof(unsigned long long)));
   }
   if ((mode == 1 || mode == 3) && !pf->cut_auto_dev) {
-    void* hv = nullptr;
-    TRY(dalloc(&pf->cut_auto_dev, 2));
+    TRY(pf->cut_auto_dev.alloc(2));
     HIPCHK(hipMemset(pf->cut_auto_dev, 0, 2 * sizeof(unsigned long long)));
-    TRY(halloc(&pf->cut_auto_host, 2, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(&hv, pf->cut_auto_host, 0));
-    pf->cut_auto_hdev = (unsigned long long*)hv;
+    TRY(pf->cut_auto_host.alloc_mapped(2));
   }
   pf->obs_cutoff = mode != 0;
   pf->sp_stats_on = mode == 2;
@@ -760,36 +704,20 @@ int gpmdm_bank_observation(gpmdm_pf_t pf, double* mean, double* spread, void* st
   HIPCHK(hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
   const int D = m->D, F = pf->F;
-  if (!pf->ro_part) TRY(dalloc(&pf->ro_part, readout_part_doubles(pf->Pf, D, F)));
-  if (!pf->ro_obs) TRY(dalloc(&pf->ro_obs, (size_t)2 * D * F));
-  if (!pf->ro_obs_pin) TRY(halloc(&pf->ro_obs_pin, (size_t)2 * D * F, 0));
-  if (!pf->ro_obs_ev) HIPCHK(hipEventCreateWithFlags(&pf->ro_obs_ev, hipEventDisableTiming));
+  TRY(pf->ro_part.grow(readout_part_doubles(pf->Pf, D, F), s));
+  TRY(pf->ro_obs.reserve((size_t)2 * D * F, s));
   // the particles the filter holds now (X: written by the resample only; a pending pre-switch
   // reads it too and stays pending)
-  ReadoutParams rp{};
-  rp.X = pf->X;
-  rp.P = pf->Pf;
-  rp.F = F;
-  rp.d = m->d;
-  rp.D = D;
-  rp.ls = m->y_ls_dev;
-  rp.Xrec = m->obs.Xrec;
-  rp.nks = ksteps((int)m->N);
-  rp.Bro = m->ro_beta;
-  rp.n_groups = readout_groups(D);
-  rp.part = pf->ro_part;
-  rp.out = pf->ro_obs;
-  launch_obs_readout(rp, s);
+  launch_obs_readout(pose_readout(pf, pf->X, pf->ro_part, pf->ro_obs.dev), s);
   HIPCHK(hipGetLastError());
-  if (!mean && !spread) {              // launched only (timing): the handle's lifecycle waits for it
-    HIPCHK(hipEventRecord(pf->ro_obs_ev, s));
-    pf->ro_obs_pending = true;
+  if (!mean && !spread) return pf->ro_obs.leave_pending(s);   // launched only (timing)
+  auto copy = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(pf->ro_obs.pin, pf->ro_obs.dev, sizeof(double) * 2 * D * F, hipMemcpyDeviceToHost, s));
     return GPMDM_OK;
-  }
-  HIPCHK(hipMemcpyAsync(pf->ro_obs_pin, pf->ro_obs, sizeof(double) * 2 * D * F, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  };
+  TRY(pf->ro_obs.finish(copy(), s));
   for (int f = 0; f < F; ++f) {        // device rows are {mean[D], spread[D]} per filter
-    const double* row = pf->ro_obs_pin + (size_t)f * 2 * D;
+    const double* row = pf->ro_obs.pin + (size_t)f * 2 * D;
     if (mean) std::memcpy(mean + (size_t)f * D, row, sizeof(double) * D);
     if (spread) std::memcpy(spread + (size_t)f * D, row + D, sizeof(double) * D);
   }
@@ -798,13 +726,7 @@ int gpmdm_bank_observation(gpmdm_pf_t pf, double* mean, double* spread, void* st
 
 int gpmdm_pf_obs_cutoff_auto(gpmdm_pf_t pf, int* last_cut, double* fraction) {
   CHECK(pf, "null handle");
-  if (pf->cut_auto_pending) {          // the last cutoff frame's counters (as the next frame reads them)
-    HIPCHK(pf->wait_readout(pf->cut_auto_seq));
-    const unsigned long long run = __atomic_load_n(pf->cut_auto_host + 0, __ATOMIC_ACQUIRE);
-    const unsigned long long dense = __atomic_load_n(pf->cut_auto_host + 1, __ATOMIC_ACQUIRE);
-    pf->cut_auto_frac = dense ? (double)run / (double)dense : 0.0;
-    pf->cut_auto_pending = false;
-  }
+  HIPCHK(pf->cut_auto_collect());
   if (last_cut) *last_cut = pf->cut_frame ? 1 : 0;
   if (fraction) *fraction = pf->cut_auto_frac;
   return GPMDM_OK;
@@ -860,73 +782,22 @@ int gpmdm_pf_predict(gpmdm_pf_t pf, double* mean, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int C = m->C, d = m->d;
   const long long P = pf->P;
-  const size_t qn = (size_t)pf->nparts_dyn_max * P;
-  if (pf->pred_q_cap < qn) {
-    dfree(pf->pred_q);
-    TRY(dalloc(&pf->pred_q, qn));
-    pf->pred_q_cap = qn;
-  }
-  if (!pf->pred_mu) {
-    TRY(dalloc(&pf->pred_mu, (size_t)P * d));
-    TRY(dalloc(&pf->pred_mu_p, (size_t)P * d));
-    TRY(dalloc(&pf->pred_out, (size_t)pf->F * d));
-  }
+  TRY(pf->pred_q.grow((size_t)pf->nparts_dyn_max * P, s));
+  TRY(pf->pred_mu.grow((size_t)P * d, s));
+  TRY(pf->pred_mu_p.grow((size_t)P * d, s));
+  TRY(pf->pred_out.grow((size_t)pf->F * d, s));
   // group the current particles by their current class (perm / block tables are the
   // switch's scratch, rebuilt by the next switch; the class tables are predict's own)
-  const int tb = gpmdm_pf::kPredictTables;
-  const int nbs = (int)cdiv(P, 256);
+  const ClassTables tb = pf->tables(gpmdm_pf::kPredictTables);
+  const std::vector<GpImage>& dset = m->dyn_set(true);
   launch_class_hist(pf->cls, P, C, pf->blockcounts, s);
   ScanArgs sc{};
-  sc.nb = nbs;
-  sc.C = C;
-  sc.pt = m->dyn_set(true)[0].geo.pt();
-  sc.lo = 0;
-  sc.hi = P;
-  sc.blockcounts = pf->blockcounts;
-  sc.cls_new = pf->cls;
-  sc.blockoff = pf->blockoff;
-  sc.class_start = pf->class_start(tb);
-  sc.counts = pf->counts(tb);
-  sc.seg_pos_begin = pf->seg_begin(tb);
-  sc.seg_pos_end = pf->seg_end(tb);
-  sc.seg_out_base = pf->seg_out(tb);
-  sc.seg_tile_start = pf->seg_tiles(tb);
-  launch_scan_counts(sc, s);
   GroupArgs ga{};
-  ga.P = P;
-  ga.n = P;
-  ga.C = C;
-  ga.cls_new = pf->cls;
-  ga.class_start = pf->class_start(tb);
-  ga.blockoff = pf->blockoff;
-  ga.perm = pf->perm;
+  fill_grouping(sc, ga, tb, pf->blockcounts, pf->blockoff, pf->perm, pf->cls, P, C, dset[0].geo.pt());
+  launch_scan_counts(sc, s);
   launch_group(ga, s);
   // each class's dynamics-GP mean (gpmdm.py:1032-1068), rows in grouped order
-  for (int c0 = 0; c0 < C; c0 += kMaxSeg) {
-    const int ns = std::min(kMaxSeg, C - c0);
-    TileParams tp{};
-    int njm = 0;
-    for (int k = 0; k < ns; ++k) {
-      tp.seg[k] = m->dyn_set(true)[c0 + k].seg();
-      njm = std::max(njm, m->dyn_set(true)[c0 + k].n_j);
-    }
-    tp.n_seg = ns;
-    tp.geo = m->dyn_set(true)[c0].geo;
-    tp.tiles_ub = (int)(cdiv(P, tp.geo.pt()) + ns);
-    tp.n_j_max = njm;
-    tp.seg_pos_begin = pf->seg_begin(tb) + c0;
-    tp.seg_pos_end = pf->seg_end(tb) + c0;
-    tp.seg_out_base = pf->seg_out(tb) + c0;
-    tp.seg_tile_start = pf->seg_tiles(tb) + c0;
-    tp.perm = pf->perm;
-    tp.X = pf->X;
-    fill_tile_common(tp, m, true);
-    tp.qpart = pf->pred_q;
-    tp.ld_q = P;
-    tp.mu = pf->pred_mu;
-    tp.ld_mu = d;
-    launch_gp_tile(tp, d, true, s);
-  }
+  launch_dyn_tiles(m, dset, dset[0].geo, tb.seg(), pf->perm, pf->X, P, pf->pred_q, P, pf->pred_mu, s);
   launch_predict_mean(pf->perm, pf->pred_mu, pf->pred_mu_p, pf->pred_out, P, pf->Pf, pf->F, d, s);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(pf->rpin, pf->pred_out, sizeof(double) * pf->F * d, hipMemcpyDeviceToHost, s));

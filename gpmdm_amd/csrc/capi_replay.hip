@@ -24,13 +24,13 @@ int gpmdm_pf_draws_free(gpmdm_pf_t pf, int which) {
   CHECK(pf->rng_mode == GPMDM_RNG_REPLAY, "draw buffers belong to replay filters");
   CHECK(which >= 0 && which < 3, "which: 0 exp draws, 1 normals, 2 uniforms");
   HIPCHK(hipSetDevice(pf->m->device));
-  HIPCHK(hipEventSynchronize(pf->rep_ev[which]));
-  if (pf->seq_pin && pf->rep_dev[which] && pf->rep_src[which] == pf->rep_dev[which]) {
+  HIPCHK(pf->rep_ev[which].sync());
+  if (pf->seq_pin && pf->rep_pin[which].dev && pf->rep_src[which] == pf->rep_pin[which].dev) {
     HIPCHK(pf->wait_readout(pf->ro_seq));   // last read in place: guarded by the read-out number (draws_used)
     // a replay pre-switch launched after that read-out reads the Exp(1) draws in place too:
     // its class counts (published after its switch) follow that read
     if (which == 0 && pf->preswitched && pf->pre_counts)
-      HIPCHK(pf->pre_counts_seq ? pf->wait_counts() : hipEventSynchronize(pf->cnt_done));
+      HIPCHK(pf->pre_counts_seq ? pf->wait_counts() : pf->cnt_done.sync());
   }
   return GPMDM_OK;
 }
@@ -45,16 +45,16 @@ int gpmdm_pf_stage_normals(gpmdm_pf_t pf, const double* normals, int64_t begin, 
   HIPCHK(hipSetDevice(pf->m->device));
   const size_t bytes = sizeof(double) * (size_t)(end - begin);
   if (normals != pf->rep_pin[1]) {    // into the staging buffer once its previous readers have run
-    HIPCHK(hipEventSynchronize(pf->rep_ev[1]));
+    HIPCHK(pf->rep_ev[1].sync());
     std::memcpy(pf->rep_pin[1] + begin, normals + begin, bytes);
   }
   HIPCHK(pf->make_up_stream());
   // on the side stream, after the device copy's last reader (ndev_ev: the last dynamics
   // finish), so a copy staged between frames runs beside the frame still on `stream`
-  HIPCHK(hipStreamWaitEvent(pf->up_stream, pf->ndev_ev, 0));
+  HIPCHK(pf->ndev_ev.block(pf->up_stream));
   HIPCHK(hipMemcpyAsync(pf->normals + begin, pf->rep_pin[1] + begin, bytes, hipMemcpyHostToDevice, pf->up_stream));
-  HIPCHK(hipEventRecord(pf->up_ev, pf->up_stream));
-  HIPCHK(hipStreamWaitEvent(s, pf->up_ev, 0));
+  HIPCHK(pf->up_ev.record(pf->up_stream));
+  HIPCHK(pf->up_ev.block(s));
   HIPCHK(pf->draws_used(1, pf->up_stream));   // the staging buffer's reader: the copy
   if (pf->nstage_ptr != normals) {
     pf->nstage_ptr = normals;
@@ -81,9 +81,9 @@ int gpmdm_pf_preswitch(gpmdm_pf_t pf, const double* E, void* stream) {
     // the draws go up beside the frame still running on `stream` (upload_draws first waits
     // for the last switch, the device copy's only reader); the switch waits for them
     HIPCHK(pf->upload_draws(0, pf->E, E, (size_t)pf->P * pf->m->C, pf->up_stream));
-    HIPCHK(hipEventRecord(pf->up_ev, pf->up_stream));
-    HIPCHK(hipStreamWaitEvent(s, pf->up_ev, 0));
-    TRY(do_switch(pf, E, nullptr, s, false, pf->cnt_done != nullptr, true));
+    HIPCHK(pf->up_ev.record(pf->up_stream));
+    HIPCHK(pf->up_ev.block(s));
+    TRY(do_switch(pf, E, nullptr, s, false, true, true));   // (replay: the counts ahead)
     pf->pre_E = E;
   }
   pf->sw_stream = s;

@@ -16,14 +16,10 @@ static size_t ring_bytes(long long P, int d, int L) {
 
 int sm_wait(gpmdm_pf* pf) {
   if (pf->sm_pending) {
-    HIPCHK(hipEventSynchronize(pf->sm_ev));
+    HIPCHK(pf->sm_ev.sync());
     pf->sm_pending = false;
   }
-  if (pf->sm_tr_pending) {
-    HIPCHK(hipEventSynchronize(pf->sm_tr_ev));
-    pf->sm_tr_pending = false;
-  }
-  return GPMDM_OK;
+  return pf->sm_out.wait();
 }
 
 static void launch_record(gpmdm_pf* pf, hipStream_t s) {
@@ -46,7 +42,7 @@ int sm_record(gpmdm_pf* pf, hipStream_t s) {
   HIPCHK(hipGetLastError());
   // (a frame counter that wrapped starts a new history: slots follow the counter)
   pf->sm_depth = pf->frame == 0 ? 0 : std::min(pf->sm_L, pf->sm_depth + 1);
-  HIPCHK(hipEventRecord(pf->sm_ev, s));
+  HIPCHK(pf->sm_ev.record(s));
   pf->sm_pending = true;
   pf->sm_stream = s;
   return GPMDM_OK;
@@ -76,18 +72,17 @@ int sm_set(gpmdm_pf* pf, int lag) {
   // read-out; a pending pre-switch reads the cloud only, and stays pending)
   TRY(sm_wait(pf));
   HIPCHK(pf->zslot_free());
-  dfree(pf->sm_anc);
-  dfree(pf->sm_cls);
-  dfree(pf->sm_X);
+  auto drop_ring = [&] {
+    pf->sm_anc.release();
+    pf->sm_cls.release();
+    pf->sm_X.release();
+  };
+  drop_ring();
   pf->sm_L = pf->sm_depth = 0;
   if (lag == 0) return GPMDM_OK;
-  if (!pf->sm_ev) HIPCHK(hipEventCreateWithFlags(&pf->sm_ev, hipEventDisableTiming));
-  if (!pf->sm_tr_ev) HIPCHK(hipEventCreateWithFlags(&pf->sm_tr_ev, hipEventDisableTiming));
   const size_t n = (size_t)(lag + 1) * pf->P;
-  if (dalloc(&pf->sm_anc, n) || dalloc(&pf->sm_cls, n) || dalloc(&pf->sm_X, n * m->d)) {
-    dfree(pf->sm_anc);
-    dfree(pf->sm_cls);
-    dfree(pf->sm_X);
+  if (pf->sm_anc.alloc(n) || pf->sm_cls.alloc(n) || pf->sm_X.alloc(n * m->d)) {
+    drop_ring();
     return GPMDM_E_NOMEM;
   }
   pf->sm_L = lag;
@@ -123,28 +118,24 @@ static int smoothed(gpmdm_pf* pf, int lag_first, int lag_last, const gpmdm_smoot
                                                                (o.ancestors ? sizeof(int) : 0) +
                                                                (o.classes ? sizeof(int) : 0));
   CHECK(stage <= kSmoothBytes, stage_refusal);
-  TRY(grow(pf->sm_marks, pf->sm_marks_cap, cnt_bytes + n_rows * ldm, s));
-  TRY(grow(pf->sm_part, pf->sm_part_cap, n_rows * nbf * d, s));
+  TRY(pf->sm_marks.grow(cnt_bytes + n_rows * ldm, s));
+  TRY(pf->sm_part.grow(n_rows * nbf * d, s));
   const size_t n_out = n_rows * W + n_rows * 2 * D;   // the rows, then {mean[D], spread[D]} of every row
-  if (pf->sm_out_cap < n_out) {
-    hfree(pf->sm_pin);
-    TRY(grow(pf->sm_out, pf->sm_out_cap, n_out, s));
-    TRY(halloc(&pf->sm_pin, n_out, 0));
-  }
-  if (obs && !pf->sm_ro_part) TRY(dalloc(&pf->sm_ro_part, readout_part_doubles(Pf, D, F)));
+  TRY(pf->sm_out.reserve(n_out, s));
+  if (obs) TRY(pf->sm_ro_part.grow(readout_part_doubles(Pf, D, F), s));
   // per-call staging of the particle rows, released in the stream's order on every exit
-  double* stage_X = nullptr;
-  int *stage_anc = nullptr, *stage_cls = nullptr;
+  DevBuf<double> stage_X;
+  DevBuf<int> stage_anc, stage_cls;
   int rc = GPMDM_OK;
-  if (want_X) rc = dalloc(&stage_X, (size_t)n * P * d);
-  if (rc == GPMDM_OK && o.ancestors) rc = dalloc(&stage_anc, (size_t)n * P);
-  if (rc == GPMDM_OK && o.classes) rc = dalloc(&stage_cls, (size_t)n * P);
+  if (want_X) rc = stage_X.alloc((size_t)n * P * d);
+  if (rc == GPMDM_OK && o.ancestors) rc = stage_anc.alloc((size_t)n * P);
+  if (rc == GPMDM_OK && o.classes) rc = stage_cls.alloc((size_t)n * P);
   std::vector<int> a32, c32;
-  double* out_ro = pf->sm_out + n_rows * W;
+  double* out_ro = pf->sm_out.dev + n_rows * W;
   auto launches = [&]() -> int {
     // the record of the latest frame, if it ran on another stream
-    if (pf->sm_pending && pf->sm_stream != s) HIPCHK(hipStreamWaitEvent(s, pf->sm_ev, 0));
-    int* counts = reinterpret_cast<int*>(pf->sm_marks);
+    if (pf->sm_pending && pf->sm_stream != s) HIPCHK(pf->sm_ev.block(s));
+    int* counts = reinterpret_cast<int*>(pf->sm_marks.p);
     unsigned char* marks = pf->sm_marks + cnt_bytes;
     HIPCHK(hipMemsetAsync(pf->sm_marks, 0, cnt_bytes + n_rows * ldm, s));
     SmTraceArgs ta{};
@@ -172,13 +163,13 @@ static int smoothed(gpmdm_pf* pf, int lag_first, int lag_last, const gpmdm_smoot
     ra.partials = pf->sm_part;
     ra.marks = marks;
     ra.ld_marks = ldm;
-    ra.out = pf->sm_out;
+    ra.out = pf->sm_out.dev;
     ra.ld_out = W;
     launch_sm_reduce(ra, n, F, s);
     for (int r = 0; obs && r < n; ++r)   // each lag's pose: one read-out over the F traced clouds
-      launch_obs_readout(rollout_readout(pf, stage_X + (size_t)r * P * d, pf->sm_ro_part, out_ro + (size_t)r * F * 2 * D), s);
+      launch_obs_readout(pose_readout(pf, stage_X + (size_t)r * P * d, pf->sm_ro_part, out_ro + (size_t)r * F * 2 * D), s);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(pf->sm_pin, pf->sm_out, sizeof(double) * (obs ? n_out : n_rows * W), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pf->sm_out.pin, pf->sm_out.dev, sizeof(double) * (obs ? n_out : n_rows * W), hipMemcpyDeviceToHost, s));
     if (o.states) HIPCHK(hipMemcpyAsync(o.states, stage_X, sizeof(double) * n * P * d, hipMemcpyDeviceToHost, s));
     if (o.ancestors) {
       a32.resize((size_t)n * P);
@@ -191,17 +182,14 @@ static int smoothed(gpmdm_pf* pf, int lag_first, int lag_last, const gpmdm_smoot
     return GPMDM_OK;
   };
   if (rc == GPMDM_OK) rc = launches();
-  pf->sm_tr_pending = hipEventRecord(pf->sm_tr_ev, s) == hipSuccess;   // (quiesce waits if the wait below fails)
-  if (stage_X) dfree_after(stage_X, s);
-  if (stage_anc) dfree_after(stage_anc, s);
-  if (stage_cls) dfree_after(stage_cls, s);
-  if (rc != GPMDM_OK) return rc;
-  HIPCHK(hipStreamSynchronize(s));
-  pf->sm_tr_pending = false;
+  stage_X.release_after(s);
+  stage_anc.release_after(s);
+  stage_cls.release_after(s);
+  TRY(pf->sm_out.finish(rc, s));         // (quiesce waits for the launches if the wait fails)
   if (pf->sm_pending && pf->sm_stream == s) pf->sm_pending = false;   // (the record preceded the trace on s)
-  const double* ro = pf->sm_pin + n_rows * W;
+  const double* ro = pf->sm_out.pin + n_rows * W;
   for (size_t q = 0; q < n_rows; ++q) {
-    const double* row = pf->sm_pin + q * W;
+    const double* row = pf->sm_out.pin + q * W;
     if (o.class_prob) std::memcpy(o.class_prob + q * C, row, sizeof(double) * C);
     if (o.state_mean) std::memcpy(o.state_mean + q * d, row + C, sizeof(double) * d);
     if (o.distinct) o.distinct[q] = (int64_t)row[C + d];
