@@ -177,7 +177,8 @@ __device__ __forceinline__ void publish_seq(long long* p, long long v) {
 }
 
 // Wave (64-lane) reductions.
-__device__ __forceinline__ double wave_sum(double v) {
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   return v;
@@ -186,6 +187,136 @@ __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
   return v;
+}
+__device__ __forceinline__ unsigned long long wave_max_key(unsigned long long key) {   // ord_enc keys
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long y = __shfl_xor(key, off);
+    key = y > key ? y : key;
+  }
+  return key;
+}
+
+// The maximum of a workgroup's keys (NW waves; wk: NW keys of LDS), in every thread.  The max of a
+// set in ord_enc's total order does not depend on how the set is split.
+template <int NW>
+__device__ __forceinline__ unsigned long long block_max_key(unsigned long long key, unsigned long long* wk) {
+  key = wave_max_key(key);
+  if ((threadIdx.x & 63) == 0) wk[threadIdx.x >> 6] = key;
+  __syncthreads();
+  unsigned long long m = wk[0];
+  for (int i = 1; i < NW; ++i) m = wk[i] > m ? wk[i] : m;
+  return m;
+}
+// ... into bmax[blockIdx.x]: the block maxima that k_norm_exp_scan reads instead of k_norm_max's
+// atomicMax result (the same value exactly).  Every thread of the workgroup calls it.
+template <int NW>
+__device__ __forceinline__ void block_max_key_store(unsigned long long key, unsigned long long* bmax) {
+  __shared__ unsigned long long wk[NW];
+  const unsigned long long m = block_max_key<NW>(key, wk);
+  if (threadIdx.x == 0) bmax[blockIdx.x] = m;
+}
+
+// Scans.  The operation decides the association: a double sum keeps the form its caller names.
+struct OpSum {
+  template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+};
+struct OpMax {
+  template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a > b ? a : b; }
+};
+// Inclusive scan over the first N lanes of a wave: v = op(v, v of the lane `off` below), off = 1, 2, ..
+template <int N = 64, class T, class Op>
+__device__ __forceinline__ T wave_inclusive_scan(T v, Op op) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 1; off < N; off <<= 1) {
+    const T y = __shfl_up(v, off);
+    if (lane >= off) v = op(v, y);
+  }
+  return v;
+}
+// Inclusive scan over one block of waves (wave `wq` of it; wtot: the block's wave totals in LDS):
+// the wave scan, then op(x, (id op total_0) op total_1 ...) over the earlier waves in order.
+// Contains a barrier: every thread of the workgroup calls it.
+template <class T, class Op>
+__device__ __forceinline__ T block_inclusive_scan(T v, T id, Op op, T* wtot, int wq) {
+  T x = wave_inclusive_scan(v, op);
+  if ((threadIdx.x & 63) == 63) wtot[wq] = x;
+  __syncthreads();
+  T base = id;
+  for (int u = 0; u < wq; ++u) base = op(base, wtot[u]);
+  return op(x, base);
+}
+
+// A lane's rank among the set lanes of a wave mask, and among the lanes where pred holds
+// (*count: how many hold).
+__device__ __forceinline__ int mask_rank(unsigned long long m) {
+  return __popcll(m & ((1ull << (threadIdx.x & 63)) - 1ull));
+}
+__device__ __forceinline__ int ballot_rank(bool pred, int* count) {
+  const unsigned long long m = __ballot(pred);
+  *count = __popcll(m);
+  return mask_rank(m);
+}
+
+// Exclusive scans of one value per thread over a 1024-thread workgroup; *total = the whole.
+// Integer sums: wave shuffles, the 16 wave totals scanned by wave 0 -- two barriers instead of a
+// Hillis-Steele's twenty (any association gives the same integers).
+__device__ __forceinline__ int block1024_exclusive_sum(int x, int* total) {
+  __shared__ int wtot[16], wpre[16];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int v = wave_inclusive_scan(x, OpSum());
+  if (lane == 63) wtot[w] = v;
+  __syncthreads();
+  if (w == 0) {
+    const int t = wave_inclusive_scan<16>(lane < 16 ? wtot[lane] : 0, OpSum());
+    if (lane < 16) wpre[lane] = t;
+  }
+  __syncthreads();
+  *total = wpre[15];
+  return v - x + (w ? wpre[w - 1] : 0);
+}
+// Hillis-Steele in LDS, part[i] = op(part[i], part[i - off]): the form of the double sums, whose
+// association other code reproduces (k_small_resample's four-slot emulation).
+template <class T, class Op>
+__device__ __forceinline__ T block1024_exclusive_scan_hs(T x, T id, Op op, T* total) {
+  __shared__ T part[1024];
+  const int tid = threadIdx.x;
+  part[tid] = x;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const T v = tid >= off ? part[tid - off] : id;
+    __syncthreads();
+    part[tid] = op(part[tid], v);
+    __syncthreads();
+  }
+  *total = part[1023];
+  return tid ? part[tid - 1] : id;
+}
+// Exclusive scan of n values (in[i * stride] -> out[i * stride], in place allowed) by one
+// 1024-thread workgroup: per thread a chunk of consecutive values, `scan` over the chunk
+// totals (one of the two above, as (x, &total) -> exclusive prefix).  Returns the total.
+template <class T, class Op, class Scan>
+__device__ __forceinline__ T chunked1024_exclusive_scan(const T* in, T* out, long long stride, int n, T id, Op op,
+                                                        Scan scan) {
+  const int tid = threadIdx.x;
+  const int chunk = (n + 1023) / 1024;
+  T s = id;
+  for (int i = 0; i < chunk; ++i) {
+    const int b = tid * chunk + i;
+    if (b < n) s = op(s, in[b * stride]);
+  }
+  T total;
+  T run = scan(s, &total);
+  for (int i = 0; i < chunk; ++i) {
+    const int b = tid * chunk + i;
+    if (b < n) {
+      const T v = in[b * stride];
+      out[b * stride] = run;
+      run = op(run, v);
+    }
+  }
+  return total;
 }
 
 }  // namespace gpmdm

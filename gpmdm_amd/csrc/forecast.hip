@@ -25,22 +25,8 @@ __global__ __launch_bounds__(kB) void k_fc_switch(FcSwitchArgs a) {
   const long long g = (long long)blockIdx.x * kB + tid;
   if (g < a.P) {
     const long long f = filter_of(g, a.P, a.Pf), p = g - f * a.Pf;
-    const int c0 = a.cls[g];
-    const uint2 key = filter_key(a.seed_lo, a.seed_hi, f);
-    int best = 0;
-    double bestv = -INFINITY;
-    for (int j = 0; j < a.C; j += 2) {
-      const uint4 r = philox4x32_10(
-          make_uint4((unsigned)p, a.frame, kStreamForecastSwitch, (a.h << 8) | (unsigned)(j >> 1)), key);
-      const double e0 = -log(u01_oo(r.x, r.y));
-      const double e1 = -log(u01_oo(r.z, r.w));
-      const double v0 = a.T[c0 * a.C + j] / e0;
-      if (v0 > bestv) { bestv = v0; best = j; }
-      if (j + 1 < a.C) {
-        const double v1 = a.T[c0 * a.C + j + 1] / e1;
-        if (v1 > bestv) { bestv = v1; best = j + 1; }
-      }
-    }
+    const int best = switch_draw(a.T, a.C, a.cls[g], nullptr, 0, (unsigned)p, a.frame, kStreamForecastSwitch, a.h << 8,
+                                 filter_key(a.seed_lo, a.seed_hi, f));
     a.cls_new[g] = best;
     atomicAdd(&hist[best], 1);
   }
@@ -63,31 +49,20 @@ __global__ __launch_bounds__(kB) void k_fc_finish(FcFinishArgs a) {
   long long g = 0, f = 0, p = 0;
   double vc = 0.0;
   if (live) {
-    int c = 0;
-    for (int s = 1; s < a.C; ++s)
-      if (o >= a.seg_out_base[s]) c = s;
+    const int c = seg_of(a.seg_out_base, a.C, o);
     const long long pos = a.seg_pos_begin[c] + (o - a.seg_out_base[c]);
     g = a.perm[pos];
     f = filter_of(g, a.P, a.Pf);
     p = g - f * a.Pf;
-    if (!a.mean_only) {
-      double q = 0.0;
-      const int np = a.n_parts[c];
-      for (int k = 0; k < np; ++k) q += a.qpart[(long long)k * a.ld_q + o];
-      double kd = 0.0;
-      for (int j = 0; j < d; ++j) {
-        const double x = a.X[g * d + j];
-        kd = fma(a.lin_c2[j] * x, x, kd);
-      }
-      kd = 1.0 + (kd + a.lin_c2[d]);
-      vc = kd - q;
-    }
+    if (!a.mean_only) vc = dyn_vc(a.qpart, a.ld_q, a.n_parts[c], o, a.X + g * d, a.lin_c2, d);
   }
   for (int j = 0; j < d; j += 2) {
     double x0 = 0.0, x1 = 0.0;
     if (live) {
       double e0 = 0.0, e1 = 0.0;
       if (!a.mean_only) {
+        // k_dyn_finish's Box-Muller pair, written out in both kernels: through a shared device
+        // function this kernel took 98 VGPRs instead of 96 (occupancy 4 instead of 5)
         const uint4 r = philox4x32_10(
             make_uint4((unsigned)p, a.frame, kStreamForecastDyn, (a.h << 8) | (unsigned)(j >> 1)),
             filter_key(a.seed_lo, a.seed_hi, f));

@@ -175,12 +175,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_obs_cutoff(const CutoffParams pr
       if (!(gap > 0.0 && gap * gap > prm.cut2)) bits |= 1u << (k - k0);
     }
     const int cnt = __builtin_popcount(bits);
-    int incl = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int y = __shfl_up(incl, off);
-      if (lane >= off) incl += y;
-    }
+    const int incl = wave_inclusive_scan(cnt, OpSum());
     if (lane == 63) wtot[w] = incl;
     __syncthreads();
     int base = incl - cnt;

@@ -21,8 +21,7 @@ __global__ __launch_bounds__(kB) void k_gate_decide(const GateParams p) {
   const int D = p.ro.D, tid = threadIdx.x;
   int c = 0;
   for (int j = tid; j < D; j += kB) c += gate_exceeded(p, j) ? 1 : 0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+  c = wave_sum(c);
   if ((tid & 63) == 0) wc[tid >> 6] = c;
   __syncthreads();
   int n_ex = 0;
@@ -118,21 +117,7 @@ __global__ __launch_bounds__(kB) void k_gate_finish(const GateParams p) {
     p.ll[o] = llv;
     key = ord_enc(fmax(-INFINITY, llv));  // k_norm_max's value set: NaN ignored
   }
-  if (p.bmax) {
-    __shared__ unsigned long long wk[kB / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const unsigned long long y = __shfl_xor(key, off);
-      key = y > key ? y : key;
-    }
-    if ((threadIdx.x & 63) == 0) wk[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned long long m = wk[0];
-      for (int i = 1; i < kB / 64; ++i) m = wk[i] > m ? wk[i] : m;
-      p.bmax[blockIdx.x] = m;
-    }
-  }
+  if (p.bmax) block_max_key_store<kB / 64>(key, p.bmax);
 }
 
 void launch_gate(const GateParams& p, hipStream_t s) {

@@ -29,6 +29,55 @@ __device__ __forceinline__ uint2 filter_key(unsigned seed_lo, unsigned seed_hi, 
   return make_uint2((unsigned)(k & 0xffffffffu), (unsigned)(k >> 32));
 }
 
+// The per-particle draws of the proposal, shared by the filter's kernels (pf_kernels.hip) and the
+// forecast roll-out's (forecast.hip), which differ in the Philox stream and sub-counter only.
+//
+// The Markov switch out of class c0: torch.multinomial(T[c0], 1) == argmax_j T[c0, j] / E_j, first
+// maximum (gpmdm_pf.py:150).  E: rows of C Exp(1) draws (replay; the particle's is row e_row), or
+// nullptr: Philox, one call per two classes with the counter (pl, frame, stream, sub | j / 2).
+__device__ __forceinline__ int switch_draw(const double* T, int C, int c0, const double* E, long long e_row,
+                                           unsigned pl, unsigned frame, unsigned stream, unsigned sub, uint2 key) {
+  int best = 0;
+  double bestv = -INFINITY;
+  for (int j = 0; j < C; j += 2) {
+    double e0, e1 = 1.0;
+    if (E) {
+      e0 = E[e_row * C + j];
+      if (j + 1 < C) e1 = E[e_row * C + j + 1];
+    } else {
+      const uint4 r = philox4x32_10(make_uint4(pl, frame, stream, sub | (unsigned)(j >> 1)), key);
+      e0 = -log(u01_oo(r.x, r.y));
+      e1 = -log(u01_oo(r.z, r.w));
+    }
+    const double v0 = T[c0 * C + j] / e0;
+    if (v0 > bestv) { bestv = v0; best = j; }
+    if (j + 1 < C) {
+      const double v1 = T[c0 * C + j + 1] / e1;
+      if (v1 > bestv) { bestv = v1; best = j + 1; }
+    }
+  }
+  return best;
+}
+// The dynamics GP's predictive variance factor vc = k(x, x) - q: q summed over the np column
+// blocks' partials of tile row r, k(x, x) = 1 + [x, 1] diag(c^2) [x, 1]^T without noise
+// (gpmdm.py:1100).
+__device__ __forceinline__ double dyn_vc(const double* qpart, long long ld_q, int np, long long r, const double* x,
+                                         const double* lin_c2, int d) {
+  double q = 0.0;
+  for (int k = 0; k < np; ++k) q += qpart[(long long)k * ld_q + r];
+  double kd = 0.0;
+  for (int j = 0; j < d; ++j) kd = fma(lin_c2[j] * x[j], x[j], kd);
+  kd = 1.0 + (kd + lin_c2[d]);
+  return kd - q;
+}
+// out index o -> class segment
+__device__ __forceinline__ int seg_of(const int* seg_out_base, int n_seg, long long o) {
+  int c = 0;
+  for (int s = 1; s < n_seg; ++s)
+    if (o >= seg_out_base[s]) c = s;
+  return c;
+}
+
 struct SwitchArgs {
   long long P;                    // all particles (F * Pf)
   long long base, n;              // positions [base, base + n) of the ownership order are switched
@@ -296,13 +345,10 @@ bool uniform_order_supported(long long P);   // P <= 33.5M (larger filters keep 
 int launch_uniform_order(long long P, unsigned frame, unsigned seed_lo, unsigned seed_hi, int* own, int* inv,
                          void* temp, size_t temp_bytes, hipStream_t s);
 
-void launch_switch(const SwitchArgs& a, hipStream_t s);
 void launch_scan_counts(const ScanArgs& a, hipStream_t s);
 void launch_group(const GroupArgs& a, hipStream_t s);
-void launch_lead(const LeadArgs& a, hipStream_t s);
 void launch_dyn_finish(const DynFinishArgs& a, hipStream_t s);
 void launch_obs_finish(const ObsFinishArgs& a, hipStream_t s);
-void launch_normalise(const NormArgs& a, hipStream_t s);
 void launch_resample(const ResampleArgs& a, hipStream_t s);
 void launch_normalise_resample(const NormArgs& na, const ResampleArgs& ra, hipStream_t s);
 bool small_resample_ok(const NormArgs& na, const ResampleArgs& ra);

@@ -3,6 +3,7 @@
 //   k_switch        _propogate_markov_switching   gpmdm_pf.py:137-151
 //   k_scan_counts   class counts, per-block offsets, this rank's class segments
 //   k_group         stable class grouping (the order of gpmdm_pf.py:158-161)
+//   k_lead_*        ancestor de-duplication: leader flags, leader rows, their segment tables
 //   k_dyn_finish    variance + sample mu + sqrt(var) eps   gpmdm.py:1062-1067, gpmdm_pf.py:167-168
 //   k_obs_finish    variance + Gaussian log-likelihood      gpmdm.py:958-961, gpmdm_pf.py:188-192
 //   k_obs_ll        the same from the tile kernel's fused partial sums (filter path)
@@ -10,6 +11,11 @@
 //   k_guide/k_resample  torch.multinomial(w, P, True) inverse CDF + gathers  gpmdm_pf.py:206-213
 //                   and the read-out partial sums            gpmdm_pf.py:224-262, 302-312
 //   k_readout       read-out totals
+//   k_small_switch, k_small_resample   the two chains in one workgroup each (P <= 1024)
+// Each step of a chain is one device function, called by its kernel of the multi-kernel path and
+// by the one-workgroup kernel with another BlockGeo and with LDS mirrors where the multi-kernel
+// path reads a buffer back; the wave and workgroup scans and maxima are common.h's, the draws
+// pf_kernels.h's (shared with forecast.hip).
 // All arithmetic is fp64; every reduction has a fixed order (bitwise run-to-run repeatable).
 #include <cstdlib>
 
@@ -21,7 +27,36 @@ namespace gpmdm {
 constexpr int kB = 256;   // threads per block of the O(P) kernels
 constexpr unsigned kMaxNormBlocks = 128;   // blocks per filter of k_norm_max
 
+// The 256-thread block of the O(P) kernels a thread stands for: a workgroup of the multi-kernel
+// path, or a quarter of a one-workgroup kernel's 1024 threads (block b = waves 4b .. 4b+3, so
+// every wave-level scan and sum sees the same lanes on either path).
+struct BlockGeo {
+  int b;    // the block
+  int t;    // the thread's index in it
+  int wq;   // its wave of the block
+};
+__device__ __forceinline__ BlockGeo grid_block() {
+  return BlockGeo{(int)blockIdx.x, (int)threadIdx.x, (int)threadIdx.x >> 6};
+}
+__device__ __forceinline__ BlockGeo quarter_block() {
+  return BlockGeo{(int)threadIdx.x >> 8, (int)threadIdx.x & 255, ((int)threadIdx.x >> 6) & 3};
+}
+
+// The de-duplication key of particle p with new class c and in-filter ancestor anc.
+__device__ __forceinline__ long long dedup_key(long long P, long long Pf, int c, long long p, int anc) {
+  return (long long)c * P + (p / Pf) * Pf + anc;
+}
+
 // ---------------------------------------------------------------------------------
+// The switch of particle p: its new class, stored.
+__device__ __forceinline__ int switch_particle(const SwitchArgs& a, long long p) {
+  const long long f = p / a.Pf;
+  const int best = switch_draw(a.T, a.C, a.cls[p], a.E, p, (unsigned)(p - f * a.Pf), a.frame,
+                               kStreamSwitch, 0u, filter_key(a.seed_lo, a.seed_hi, f));
+  a.cls_new[p] = best;
+  return best;
+}
+
 // OWN: ancestor-ordered shards (thread i handles particle own[i]); the identity
 // instantiation keeps p == i visible to the compiler (one-rank path unchanged).
 template <bool OWN>
@@ -38,38 +73,15 @@ __global__ __launch_bounds__(kB) void k_switch(SwitchArgs a) {
   if (t < a.n) {
     const long long p = OWN ? (long long)a.own[i] : i;
     pid = (unsigned)p;
-    const int c0 = a.cls[p];
-    const long long f = p / a.Pf;
-    const uint2 key = filter_key(a.seed_lo, a.seed_hi, f);
-    const unsigned pl = (unsigned)(p - f * a.Pf);
-    int best = 0;
-    double bestv = -INFINITY;
-    for (int j = 0; j < a.C; j += 2) {
-      double e0, e1 = 1.0;
-      if (a.E) {
-        e0 = a.E[p * a.C + j];
-        if (j + 1 < a.C) e1 = a.E[p * a.C + j + 1];
-      } else {
-        const uint4 r = philox4x32_10(make_uint4(pl, a.frame, kStreamSwitch, (unsigned)(j >> 1)), key);
-        e0 = -log(u01_oo(r.x, r.y));
-        e1 = -log(u01_oo(r.z, r.w));
-      }
-      // torch.multinomial(p, 1) == argmax(p / E), first maximum (gpmdm_pf.py:150)
-      const double v0 = a.T[c0 * a.C + j] / e0;
-      if (v0 > bestv) { bestv = v0; best = j; }
-      if (j + 1 < a.C) {
-        const double v1 = a.T[c0 * a.C + j + 1] / e1;
-        if (v1 > bestv) { bestv = v1; best = j + 1; }
-      }
-    }
-    a.cls_new[p] = best;
+    const int best = switch_particle(a, p);
     atomicAdd(&hist[best], 1);
-    if (a.owner && i >= a.lo && i < a.hi) dkey = (long long)best * a.P + f * a.Pf + a.anc[p];
+    if (a.owner && i >= a.lo && i < a.hi) dkey = dedup_key(a.P, a.Pf, best, p, a.anc[p]);
   }
   if (a.owner) {
     // Leader election: one atomicMin per distinct key per wave (its lowest lane), so a
     // collapsed cloud (every particle one ancestor) does not serialise P atomics on one
     // address.  The leader is deterministic; which particle leads does not change any value.
+    // (k_small_switch, at most 1024 particles, issues one atomicMin per particle instead.)
     const int lane = tid & 63;
     unsigned long long pending = __ballot(dkey >= 0);
     while (pending) {
@@ -87,59 +99,39 @@ __global__ __launch_bounds__(kB) void k_switch(SwitchArgs a) {
 }
 
 // ---------------------------------------------------------------------------------
-// Exclusive scan of one int per thread over a 1024-thread workgroup: wave shuffles, the 16
-// wave totals scanned by wave 0 -- two barriers instead of a 1024-wide Hillis-Steele's
-// twenty (integer sums: any association gives the same result).  Returns the exclusive
-// prefix of x; *total = the sum over the workgroup.  wtot / wpre: 16 ints of LDS each.
-__device__ __forceinline__ int block1024_exclusive_scan(int x, int* wtot, int* wpre, int* total) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  int v = x;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(v, off);
-    if (lane >= off) v += y;
+// One thread: the class table pass.  tot / lo_cnt / hi_cnt: per class its particles, and those
+// among positions [0, lo) and [0, hi) of the ownership order.  class_start and seg_t: C + 1.
+__device__ __forceinline__ void class_seg_tables(int C, int pt, const int* tot, const int* lo_cnt, const int* hi_cnt,
+                                                 int* class_start, int* seg_b, int* seg_e, int* seg_o, int* seg_t,
+                                                 int* counts, int* counts_host) {
+  int cs = 0, ob = 0, ts = 0;
+  for (int c = 0; c < C; ++c) {
+    class_start[c] = cs;
+    if (counts) counts[c] = tot[c];
+    if (counts_host) counts_host[c] = tot[c];
+    const int b0 = cs + lo_cnt[c], e0 = cs + hi_cnt[c];
+    seg_b[c] = b0;
+    seg_e[c] = e0;
+    seg_o[c] = ob;
+    seg_t[c] = ts;
+    ob += e0 - b0;
+    ts += (e0 - b0 + pt - 1) / pt;
+    cs += tot[c];
   }
-  if (lane == 63) wtot[w] = v;
-  __syncthreads();
-  if (w == 0) {
-    int t = lane < 16 ? wtot[lane] : 0;
-#pragma unroll
-    for (int off = 1; off < 16; off <<= 1) {
-      const int y = __shfl_up(t, off);
-      if (lane >= off) t += y;
-    }
-    if (lane < 16) wpre[lane] = t;
-  }
-  __syncthreads();
-  *total = wpre[15];
-  return v - x + (w ? wpre[w - 1] : 0);
+  class_start[C] = cs;
+  seg_t[C] = ts;
 }
 
 // One workgroup: exclusive scans of the per-block class counts, class starts, and the
 // segments (grouped position ranges) of this rank's particle slice [lo, hi).
-// (a device function: k_small_switch runs the same body inside its workgroup)
-__device__ __forceinline__ void scan_counts_body(const ScanArgs& a) {
-  __shared__ int wtot[16], wpre[16];
+__global__ __launch_bounds__(1024) void k_scan_counts(ScanArgs a) {
   __shared__ int tot[kMaxClasses];
   __shared__ int lo_cnt[kMaxClasses], hi_cnt[kMaxClasses];
   const int tid = threadIdx.x;
   const int nb = a.nb;
-  const int chunk = (nb + 1023) / 1024;
   for (int c = 0; c < a.C; ++c) {
-    int s = 0;
-    for (int i = 0; i < chunk; ++i) {
-      const int b = tid * chunk + i;
-      if (b < nb) s += a.blockcounts[(long long)b * a.C + c];
-    }
-    int total;
-    int run = block1024_exclusive_scan(s, wtot, wpre, &total);
-    for (int i = 0; i < chunk; ++i) {
-      const int b = tid * chunk + i;
-      if (b < nb) {
-        a.blockoff[(long long)b * a.C + c] = run;
-        run += a.blockcounts[(long long)b * a.C + c];
-      }
-    }
+    const int total = chunked1024_exclusive_scan(a.blockcounts + c, a.blockoff + c, a.C, nb, 0, OpSum(),
+                                                 [](int x, int* t) { return block1024_exclusive_sum(x, t); });
     if (tid == 0) tot[c] = total;
   }
   __syncthreads();
@@ -163,49 +155,43 @@ __device__ __forceinline__ void scan_counts_body(const ScanArgs& a) {
     __syncthreads();
   }
   if (tid == 0) {
-    int cs = 0, ob = 0, ts = 0;
-    for (int c = 0; c < a.C; ++c) {
-      a.class_start[c] = cs;
-      a.counts[c] = tot[c];
-      if (a.counts_host) a.counts_host[c] = tot[c];
-      const int b0 = cs + lo_cnt[c], e0 = cs + hi_cnt[c];
-      a.seg_pos_begin[c] = b0;
-      a.seg_pos_end[c] = e0;
-      a.seg_out_base[c] = ob;
-      a.seg_tile_start[c] = ts;
-      ob += e0 - b0;
-      ts += (e0 - b0 + a.pt - 1) / a.pt;
-      cs += tot[c];
-    }
+    class_seg_tables(a.C, a.pt, tot, lo_cnt, hi_cnt, a.class_start, a.seg_pos_begin, a.seg_pos_end, a.seg_out_base,
+                     a.seg_tile_start, a.counts, a.counts_host);
     if (a.counts_seq_host)              // the host waits on this number, not on an event
       publish_seq(a.counts_seq_host, a.counts_seq);   // (this thread wrote counts_host above)
-    a.class_start[a.C] = cs;
-    a.seg_tile_start[a.C] = ts;
   }
 }
-__global__ __launch_bounds__(1024) void k_scan_counts(ScanArgs a) { scan_counts_body(a); }
 
 // ---------------------------------------------------------------------------------
+// The stable class grouping of one block: the grouped position of the thread's particle of
+// class c (c < 0: no particle, returns -1).  wcount: the block's wave counts per class (LDS);
+// blockoff: the block's row of class offsets.  Contains a barrier.
+__device__ __forceinline__ int group_position(int c, int C, BlockGeo g, int (*wcount)[kMaxClasses],
+                                              const int* class_start, const int* blockoff) {
+  int rank = 0;
+  for (int k = 0; k < C; ++k) {
+    int n;
+    const int r = ballot_rank(c == k, &n);
+    if (c == k) rank = r;
+    if ((g.t & 63) == 0) wcount[g.wq][k] = n;
+  }
+  __syncthreads();
+  if (c < 0) return -1;
+  int off = class_start[c] + blockoff[c];
+  for (int v = 0; v < g.wq; ++v) off += wcount[v][c];
+  return off + rank;
+}
+
 template <bool OWN>
 __global__ __launch_bounds__(kB) void k_group(GroupArgs a) {
   __shared__ int wcount[kB / 64][kMaxClasses];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const long long t = (long long)blockIdx.x * kB + tid;
+  const long long t = (long long)blockIdx.x * kB + threadIdx.x;
   const long long i = a.base + t;                         // position in the ownership order
   const long long p = t < a.n ? (OWN ? (long long)a.own[i] : i) : -1;
   const int c = p >= 0 ? a.cls_new[p] : -1;
-  int rank = 0;
-  for (int k = 0; k < a.C; ++k) {
-    const unsigned long long m = __ballot(c == k);
-    if (c == k) rank = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wcount[w][k] = __popcll(m);
-  }
-  __syncthreads();
-  if (c >= 0) {
-    int off = a.class_start[c] + a.blockoff[(long long)blockIdx.x * a.C + c];
-    for (int v = 0; v < w; ++v) off += wcount[v][c];
-    a.perm[off + rank] = (int)p;
-  }
+  const int pos = group_position(c, a.C, grid_block(), wcount, a.class_start,
+                                 a.blockoff + (long long)blockIdx.x * a.C);
+  if (pos >= 0) a.perm[pos] = (int)p;
 }
 
 // ---------------------------------------------------------------------------------
@@ -217,93 +203,88 @@ __global__ __launch_bounds__(kB) void k_group(GroupArgs a) {
 // position order, so leader rows of class c are contiguous and the tile kernel's segment
 // tables keep their meaning.  Per-particle arithmetic is independent of which rows share a
 // tile, so the results are bitwise those of the undeduplicated path.
-__device__ __forceinline__ int lead_flag(const LeadArgs& a, long long pos) {
-  if (pos >= a.npos) return 0;
-  const long long p = a.perm[pos];
-  // only this rank's slice registered owners, so owner == p also means "p is in the slice"
-  const long long f = p / a.Pf;
-  return a.owner[(long long)a.cls_new[p] * a.P + f * a.Pf + a.anc[p]] == (unsigned)p;
-}
-
-// flag | block-local exclusive count << 1, and leaders per block
-__global__ __launch_bounds__(kB) void k_lead_flags(LeadArgs a) {
-  __shared__ int wc[kB / 64];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const long long pos = (long long)blockIdx.x * kB + tid;
-  const int lf = lead_flag(a, pos);
-  const unsigned long long m = __ballot(lf);
-  const int excl = __popcll(m & ((1ull << lane) - 1ull));
-  if (lane == 0) wc[w] = __popcll(m);
+//
+// The lflag_scan entry of a position with leader flag lf: flag | block-local exclusive count
+// << 1.  wc: the block's wave counts (LDS), left for the caller's block total.  Contains a barrier.
+__device__ __forceinline__ int lead_flag_scan(int lf, BlockGeo g, int* wc) {
+  int n;
+  const int excl = ballot_rank(lf, &n);
+  if ((g.t & 63) == 0) wc[g.wq] = n;
   __syncthreads();
   int base = 0;
-  for (int v = 0; v < w; ++v) base += wc[v];
-  if (pos < a.npos) a.lflag_scan[pos] = ((base + excl) << 1) | lf;
-  if (tid == 0) {
+  for (int v = 0; v < g.wq; ++v) base += wc[v];
+  return ((base + excl) << 1) | lf;
+}
+
+__global__ __launch_bounds__(kB) void k_lead_flags(LeadArgs a) {
+  __shared__ int wc[kB / 64];
+  const long long pos = (long long)blockIdx.x * kB + threadIdx.x;
+  int lf = 0;
+  if (pos < a.npos) {
+    const long long p = a.perm[pos];
+    // only this rank's slice registered owners, so owner == p also means "p is in the slice"
+    lf = a.owner[dedup_key(a.P, a.Pf, a.cls_new[p], p, a.anc[p])] == (unsigned)p;
+  }
+  const int v = lead_flag_scan(lf, grid_block(), wc);
+  if (pos < a.npos) a.lflag_scan[pos] = v;
+  if (threadIdx.x == 0) {
     int t = 0;
-    for (int v = 0; v < kB / 64; ++v) t += wc[v];
+    for (int u = 0; u < kB / 64; ++u) t += wc[u];
     a.lblock[blockIdx.x] = t;
   }
 }
 
-// One workgroup: lblock -> exclusive offsets (in place), then the leader segment tables.
-__device__ __forceinline__ void lead_tables_body(const LeadArgs& a) {
-  __shared__ int wtot[16], wpre[16];
-  __shared__ int total;
-  const int tid = threadIdx.x;
-  const int nb = a.nb;
-  const int chunk = (nb + 1023) / 1024;
-  int s = 0;
-  for (int i = 0; i < chunk; ++i) {
-    const int b = tid * chunk + i;
-    if (b < nb) s += a.lblock[b];
+// One thread: the leader segment tables.  Leaders before position x: pre[x / kB] (its block's
+// exclusive offset) + lflag[x] >> 1, and `total` from npos on.
+__device__ __forceinline__ void lead_seg_tables(int C, int pt, long long npos, int total, const int* pre,
+                                                const int* lflag, const int* seg_b, const int* seg_e, int* lseg_b,
+                                                int* lseg_e, int* lseg_o, int* lseg_t) {
+  auto row = [&](long long x) { return x >= npos ? total : pre[x / kB] + (lflag[x] >> 1); };
+  int ts = 0;
+  for (int c = 0; c < C; ++c) {
+    const int b0 = row(seg_b[c]), e0 = row(seg_e[c]);
+    lseg_b[c] = b0;
+    lseg_e[c] = e0;
+    lseg_o[c] = b0;
+    lseg_t[c] = ts;
+    ts += (e0 - b0 + pt - 1) / pt;
   }
-  int tsum;
-  int run = block1024_exclusive_scan(s, wtot, wpre, &tsum);
-  for (int i = 0; i < chunk; ++i) {
-    const int b = tid * chunk + i;
-    if (b < nb) {
-      const int cnt = a.lblock[b];
-      a.lblock[b] = run;
-      run += cnt;
-    }
-  }
-  if (tid == 0) total = tsum;
-  __syncthreads();
-  if (tid == 0) {
-    auto row = [&](long long x) { return x >= a.npos ? total : a.lblock[x / kB] + (a.lflag_scan[x] >> 1); };
-    int ts = 0;
-    for (int c = 0; c < a.C; ++c) {
-      const int b0 = row(a.seg_pos_begin[c]), e0 = row(a.seg_pos_end[c]);
-      a.lseg_pos_begin[c] = b0;
-      a.lseg_pos_end[c] = e0;
-      a.lseg_out_base[c] = b0;
-      a.lseg_tile_start[c] = ts;
-      ts += (e0 - b0 + a.pt - 1) / a.pt;
-    }
-    a.lseg_tile_start[a.C] = ts;
-  }
+  lseg_t[C] = ts;
 }
-__global__ __launch_bounds__(1024) void k_lead_tables(LeadArgs a) { lead_tables_body(a); }
 
-__device__ __forceinline__ void lead_compact_row(const LeadArgs& a, long long pos, int first) {
+// One workgroup: lblock -> exclusive offsets (in place), then the leader segment tables.
+__global__ __launch_bounds__(1024) void k_lead_tables(LeadArgs a) {
+  const int total = chunked1024_exclusive_scan(a.lblock, a.lblock, 1, a.nb, 0, OpSum(),
+                                               [](int x, int* t) { return block1024_exclusive_sum(x, t); });
+  __syncthreads();
+  if (threadIdx.x == 0)
+    lead_seg_tables(a.C, a.pt, a.npos, total, a.lblock, a.lflag_scan, a.seg_pos_begin, a.seg_pos_end,
+                    a.lseg_pos_begin, a.lseg_pos_end, a.lseg_out_base, a.lseg_tile_start);
+}
+
+// The leader row of position pos, if it holds a leader: first (its block's first row) + the
+// block-local count.
+__device__ __forceinline__ void lead_compact_row(const LeadArgs& a, const int* lflag, const int* perm,
+                                                 const int* cls_new, const int* anc, long long pos, int first) {
   if (pos >= a.npos) return;
-  const int v = a.lflag_scan[pos];
+  const int v = lflag[pos];
   if (!(v & 1)) return;
-  const long long p = a.perm[pos];
+  const long long p = perm[pos];
   const int r = first + (v >> 1);
-  const long long f = p / a.Pf;
   a.lperm[r] = (int)p;
-  const long long key = (long long)a.cls_new[p] * a.P + f * a.Pf + a.anc[p];
+  const long long key = dedup_key(a.P, a.Pf, cls_new[p], p, anc[p]);
   a.slot[key] = r;
   if (a.owner_reset) a.owner_reset[key] = 0xffffffffu;   // the next election's preset
 }
 __global__ __launch_bounds__(kB) void k_lead_compact(LeadArgs a) {
-  lead_compact_row(a, (long long)blockIdx.x * kB + threadIdx.x, a.lblock[blockIdx.x]);
+  lead_compact_row(a, a.lflag_scan, a.perm, a.cls_new, a.anc, (long long)blockIdx.x * kB + threadIdx.x,
+                   a.lblock[blockIdx.x]);
 }
 
 // k_lead_tables + k_lead_compact in one launch (nb <= kMaxLeadBlocks): block b's first leader
 // row is the sum of the leader counts of blocks 0 .. b-1, which the block adds up itself
-// (integers: any order gives k_lead_tables's prefix); block 0 also scans every block's count
+// (integers: any order gives k_lead_tables's prefix; a re-sum per block, where k_lead_tables
+// scans once, is what saves the launch); block 0 also scans every block's count
 // and writes the leader segment tables with k_lead_tables's row rule.  Same rows, same tables.
 // Up to 1024 blocks (P <= 262,144 per launch): each block's prefix re-sum is O(nb) loads and
 // block 0's table is 4 KB of static LDS in every block; above, the two launches (ADVICE r5:
@@ -317,8 +298,7 @@ __global__ __launch_bounds__(kB) void k_lead_tables_compact(LeadArgs a) {
   const int b = blockIdx.x, nb = a.nb;
   int s = 0;
   for (int bb = tid; bb < b; bb += kB) s += a.lblock[bb];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  s = wave_sum(s);
   if (lane == 0) red[w] = s;
   __syncthreads();
   int first = 0;
@@ -326,24 +306,15 @@ __global__ __launch_bounds__(kB) void k_lead_tables_compact(LeadArgs a) {
   for (int v = 0; v < kB / 64; ++v) first += red[v];
   if (b == 0) {
     // exclusive scan of the counts: per thread a chunk of consecutive blocks, then a
-    // 256-wide scan of the chunk sums (wave shuffles + the four wave totals)
+    // 256-wide scan of the chunk sums
     const int chunk = (nb + kB - 1) / kB;
     int cs = 0;
     for (int i = 0; i < chunk; ++i) {
       const int bb = tid * chunk + i;
       if (bb < nb) cs += a.lblock[bb];
     }
-    int incl = cs;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int y = __shfl_up(incl, off);
-      if (lane >= off) incl += y;
-    }
     __syncthreads();                           // (red is reused)
-    if (lane == 63) red[w] = incl;
-    __syncthreads();
-    int run = incl - cs;
-    for (int v = 0; v < w; ++v) run += red[v];
+    int run = block_inclusive_scan(cs, 0, OpSum(), red, w) - cs;
     for (int i = 0; i < chunk; ++i) {
       const int bb = tid * chunk + i;
       if (bb < nb) {
@@ -353,55 +324,49 @@ __global__ __launch_bounds__(kB) void k_lead_tables_compact(LeadArgs a) {
     }
     if (tid == kB - 1) total_s = run;
     __syncthreads();
-    if (tid == 0) {
-      const int total = total_s;
-      auto row = [&](long long x) { return x >= a.npos ? total : pre[x / kB] + (a.lflag_scan[x] >> 1); };
-      int ts = 0;
-      for (int c = 0; c < a.C; ++c) {
-        const int b0 = row(a.seg_pos_begin[c]), e0 = row(a.seg_pos_end[c]);
-        a.lseg_pos_begin[c] = b0;
-        a.lseg_pos_end[c] = e0;
-        a.lseg_out_base[c] = b0;
-        a.lseg_tile_start[c] = ts;
-        ts += (e0 - b0 + a.pt - 1) / a.pt;
-      }
-      a.lseg_tile_start[a.C] = ts;
-    }
+    if (tid == 0)
+      lead_seg_tables(a.C, a.pt, a.npos, total_s, pre, a.lflag_scan, a.seg_pos_begin, a.seg_pos_end,
+                      a.lseg_pos_begin, a.lseg_pos_end, a.lseg_out_base, a.lseg_tile_start);
   }
-  lead_compact_row(a, (long long)b * kB + tid, first);
+  lead_compact_row(a, a.lflag_scan, a.perm, a.cls_new, a.anc, (long long)b * kB + tid, first);
 }
 
 
 // ---------------------------------------------------------------------------------
 // Small single-shard filters (all P <= kSmallSwitchP particles switched by one rank, no
 // ownership order): one 1024-thread workgroup runs the switch, the class scan, the grouping
-// and the leader compaction in one launch instead of seven (with the owner preset).  Every
-// step is integer and deterministic (the leader of a key is its smallest particle index,
-// whatever the order of the atomics; integer sums in any order are equal), the 256-thread
-// blocks of k_switch / k_group / k_lead_* are the workgroup's quarters, and what the
-// multi-kernel path reads back from its buffers is kept in LDS (the buffers are still
-// written for the later stages), so every table is the multi-kernel path's exactly
-// (tests/test_gpu_small_path.py).  The scans over at most four blocks are one thread per
-// class (or one thread) instead of 1024-wide Hillis-Steele passes.
+// and the leader compaction in one launch instead of seven (with the owner preset).  The steps
+// are the multi-kernel path's own device functions, called with the workgroup's quarters as the
+// 256-thread blocks; what that path reads back from its buffers is kept in LDS and handed to
+// the step functions in the buffers' place (the buffers are still written for the later
+// stages), so every table is the multi-kernel path's exactly (tests/test_gpu_small_path.py).
+// Three things are its own, each integer and deterministic (the leader of a key is its smallest
+// particle index, whatever the order of the atomics; integer sums in any order are equal):
+//  * one atomicMin per particle instead of k_switch's per-wave election: at most 1024 atomics;
+//  * the scans over at most four blocks are serial, one thread per class (or one thread),
+//    instead of 1024-wide passes;
+//  * the owners were set by this launch's own atomics (at L2), so the leader flags read them
+//    with an atomic load past the L1.
 constexpr long long kSmallSwitchP = 1024;
 
 __global__ __launch_bounds__(1024) void k_small_switch(SwitchArgs sa, ScanArgs sc, GroupArgs ga, LeadArgs la,
                                                        int dedup) {
   __shared__ int hist[4][kMaxClasses];        // block counts (blockcounts)
   __shared__ int boff[4][kMaxClasses];        // block offsets (blockoff)
-  __shared__ int cstart[kMaxClasses];         // class_start
+  __shared__ int cstart[kMaxClasses + 1];     // class_start
   __shared__ int lo_cnt[kMaxClasses], hi_cnt[kMaxClasses];
   __shared__ int segb[kMaxClasses], sege[kMaxClasses], sego[kMaxClasses], segt[kMaxClasses + 1];
-  __shared__ int ctot[kMaxClasses];
+  __shared__ int ctot[kMaxClasses];           // counts
   __shared__ int lsegb[kMaxClasses], lsege[kMaxClasses], lsegt[kMaxClasses + 1];
   __shared__ int wcount[4][4][kMaxClasses];
   __shared__ int wc[4][4];
-  __shared__ int lblk[4];
+  __shared__ int lblk[4], ltot;               // lblock (exclusive offsets), all leaders
   __shared__ int cls_s[kSmallSwitchP];        // cls_new
   __shared__ int anc_s[kSmallSwitchP];        // anc
   __shared__ int perm_s[kSmallSwitchP];       // perm
   __shared__ int lflag_s[kSmallSwitchP];      // lflag_scan
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, b = tid >> 8, wq = w & 3;
+  const int tid = threadIdx.x;
+  const BlockGeo g = quarter_block();
   const long long P = sa.P;
   const int C = sa.C;
   const int nb = (int)((P + kB - 1) / kB);
@@ -416,36 +381,13 @@ __global__ __launch_bounds__(1024) void k_small_switch(SwitchArgs sa, ScanArgs s
   const long long p = tid;
   int best = -1;
   if (p < P) {
-    const int c0 = sa.cls[p];
-    const long long f = p / sa.Pf;
-    const uint2 key = filter_key(sa.seed_lo, sa.seed_hi, f);
-    const unsigned pl = (unsigned)(p - f * sa.Pf);
-    best = 0;
-    double bestv = -INFINITY;
-    for (int j = 0; j < C; j += 2) {
-      double e0, e1 = 1.0;
-      if (sa.E) {
-        e0 = sa.E[p * C + j];
-        if (j + 1 < C) e1 = sa.E[p * C + j + 1];
-      } else {
-        const uint4 r = philox4x32_10(make_uint4(pl, sa.frame, kStreamSwitch, (unsigned)(j >> 1)), key);
-        e0 = -log(u01_oo(r.x, r.y));
-        e1 = -log(u01_oo(r.z, r.w));
-      }
-      const double v0 = sa.T[c0 * C + j] / e0;
-      if (v0 > bestv) { bestv = v0; best = j; }
-      if (j + 1 < C) {
-        const double v1 = sa.T[c0 * C + j + 1] / e1;
-        if (v1 > bestv) { bestv = v1; best = j + 1; }
-      }
-    }
-    sa.cls_new[p] = best;
+    best = switch_particle(sa, p);
     cls_s[p] = best;
-    atomicAdd(&hist[b][best], 1);
+    atomicAdd(&hist[g.b][best], 1);
     if (dedup) {
       const int an = sa.anc[p];
       anc_s[p] = an;
-      if (p >= sa.lo && p < sa.hi) atomicMin(&sa.owner[(long long)best * P + f * sa.Pf + an], (unsigned)p);
+      if (p >= sa.lo && p < sa.hi) atomicMin(&sa.owner[dedup_key(P, sa.Pf, best, p, an)], (unsigned)p);
     }
   }
   __syncthreads();
@@ -458,36 +400,23 @@ __global__ __launch_bounds__(1024) void k_small_switch(SwitchArgs sa, ScanArgs s
       sc.blockoff[(long long)bb * C + tid] = run;
       run += hist[bb][tid];
     }
-    cstart[tid] = run;                         // class total, until the table pass
+    ctot[tid] = run;
   }
-  // class counts among positions [0, lo) and [0, hi): the partial block by atomics
+  // class counts among positions [0, lo) and [0, hi): the partial block by atomics, then the
+  // whole blocks before it
   for (int which = 0; which < 2; ++which) {
     const long long bound = which ? sc.hi : sc.lo;
     const long long start = (bound / kB) * kB;
     if (tid < kB && start + tid < bound) atomicAdd(which ? &hi_cnt[cls_s[start + tid]] : &lo_cnt[cls_s[start + tid]], 1);
   }
   __syncthreads();
-  if (tid == 0) {
-    int cs = 0, ob = 0, ts = 0;
-    for (int c = 0; c < C; ++c) {
-      const int tot = cstart[c];
-      const long long blo = sc.lo / kB, bhi = sc.hi / kB;
-      const int lo = lo_cnt[c] + (blo < nb ? boff[blo][c] : tot);
-      const int hi = hi_cnt[c] + (bhi < nb ? boff[bhi][c] : tot);
-      cstart[c] = cs;
-      ctot[c] = tot;
-      const int b0 = cs + lo, e0 = cs + hi;
-      segb[c] = b0;
-      sege[c] = e0;
-      sego[c] = ob;
-      segt[c] = ts;
-      ob += e0 - b0;
-      ts += (e0 - b0 + sc.pt - 1) / sc.pt;
-      cs += tot;
-    }
-    segt[C] = ts;
-    hist[0][0] = cs;                           // (class_start[C]; hist is not read again)
+  if (tid < C) {
+    const long long blo = sc.lo / kB, bhi = sc.hi / kB;
+    lo_cnt[tid] += blo < nb ? boff[blo][tid] : ctot[tid];
+    hi_cnt[tid] += bhi < nb ? boff[bhi][tid] : ctot[tid];
   }
+  __syncthreads();
+  if (tid == 0) class_seg_tables(C, sc.pt, ctot, lo_cnt, hi_cnt, cstart, segb, sege, sego, segt, nullptr, nullptr);
   __syncthreads();
   // the tables, one entry per lane (a one-thread loop of stores is vectorised into wide
   // stores, which tests/test_isa_guard.py rejects)
@@ -500,75 +429,40 @@ __global__ __launch_bounds__(1024) void k_small_switch(SwitchArgs sa, ScanArgs s
     sc.seg_out_base[tid] = sego[tid];
     sc.seg_tile_start[tid] = segt[tid];
   } else if (tid == C) {
-    sc.class_start[C] = hist[0][0];
+    sc.class_start[C] = cstart[C];
     sc.seg_tile_start[C] = segt[C];
   }
   // ---- k_group ----
-  {
-    const int c = best;
-    int rank = 0;
-    for (int k = 0; k < C; ++k) {
-      const unsigned long long m = __ballot(c == k);
-      if (c == k) rank = __popcll(m & ((1ull << lane) - 1ull));
-      if (lane == 0) wcount[b][wq][k] = __popcll(m);
-    }
-    __syncthreads();
-    if (c >= 0) {
-      int off = cstart[c] + boff[b][c];
-      for (int v = 0; v < wq; ++v) off += wcount[b][v][c];
-      ga.perm[off + rank] = (int)p;
-      perm_s[off + rank] = (int)p;
-    }
+  const int gpos = group_position(best, C, g, wcount[g.b], cstart, boff[g.b]);
+  if (gpos >= 0) {
+    ga.perm[gpos] = (int)p;
+    perm_s[gpos] = (int)p;
   }
   __syncthreads();
   if (!dedup) return;
   // ---- k_lead_flags ----
-  {
-    const long long pos = p;
-    int lf = 0;
-    if (pos < la.npos) {
-      const long long q = perm_s[pos];
-      const long long f = q / la.Pf;
-      // the owners were set by this launch's atomics (at L2): read them past the L1
-      lf = __hip_atomic_load(&la.owner[(long long)cls_s[q] * la.P + f * la.Pf + anc_s[q]], __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT) == (unsigned)q;
+  int lf = 0;
+  if (p < la.npos) {
+    const long long q = perm_s[p];
+    lf = __hip_atomic_load(&la.owner[dedup_key(la.P, la.Pf, cls_s[q], q, anc_s[q])], __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT) == (unsigned)q;
+  }
+  const int lv = lead_flag_scan(lf, g, wc[g.b]);
+  if (p < la.npos) {
+    la.lflag_scan[p] = lv;
+    lflag_s[p] = lv;
+  }
+  // ---- k_lead_tables ----
+  if (tid == 0) {
+    int run = 0;
+    for (int bb = 0; bb < nb; ++bb) {
+      lblk[bb] = run;
+      for (int v = 0; v < kB / 64; ++v) run += wc[bb][v];
     }
-    const unsigned long long m = __ballot(lf);
-    const int excl = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wc[b][wq] = __popcll(m);
-    __syncthreads();
-    int base = 0;
-    for (int v = 0; v < wq; ++v) base += wc[b][v];
-    if (pos < la.npos) {
-      la.lflag_scan[pos] = ((base + excl) << 1) | lf;
-      lflag_s[pos] = ((base + excl) << 1) | lf;
-    }
-    if (tid == 0) {                            // ---- k_lead_tables (one thread) ----
-      int run = 0;
-      for (int bb = 0; bb < nb; ++bb) {
-        int t = 0;
-        for (int v = 0; v < kB / 64; ++v) t += wc[bb][v];
-        lblk[bb] = run;
-        run += t;
-      }
-    }
+    ltot = run;
   }
   __syncthreads();
-  if (tid == 0) {
-    int total = 0;
-    for (int bb = 0; bb < nb; ++bb)
-      for (int v = 0; v < kB / 64; ++v) total += wc[bb][v];
-    auto row = [&](long long x) { return x >= la.npos ? total : lblk[x / kB] + (lflag_s[x] >> 1); };
-    int ts = 0;
-    for (int c = 0; c < C; ++c) {
-      const int b0 = row(segb[c]), e0 = row(sege[c]);
-      lsegb[c] = b0;
-      lsege[c] = e0;
-      lsegt[c] = ts;
-      ts += (e0 - b0 + la.pt - 1) / la.pt;
-    }
-    lsegt[C] = ts;
-  }
+  if (tid == 0) lead_seg_tables(C, la.pt, la.npos, ltot, lblk, lflag_s, segb, sege, lsegb, lsege, lsegb, lsegt);
   __syncthreads();
   if (tid < C) {
     la.lseg_pos_begin[tid] = lsegb[tid];
@@ -578,18 +472,9 @@ __global__ __launch_bounds__(1024) void k_small_switch(SwitchArgs sa, ScanArgs s
   } else if (tid == C) {
     la.lseg_tile_start[C] = lsegt[C];
   }
-  // ---- k_lead_compact ----
+  // ---- k_lead_compact (la.owner_reset is nullptr here: the preset above is this kernel's) ----
   if (tid < nb) la.lblock[tid] = lblk[tid];
-  if (p < la.npos) {
-    const int v = lflag_s[p];
-    if (v & 1) {
-      const long long q = perm_s[p];
-      const int r = lblk[b] + (v >> 1);
-      const long long f = q / la.Pf;
-      la.lperm[r] = (int)q;
-      la.slot[(long long)cls_s[q] * la.P + f * la.Pf + anc_s[q]] = r;
-    }
-  }
+  lead_compact_row(la, lflag_s, perm_s, cls_s, anc_s, p, lblk[g.b]);
 }
 
 // ---------------------------------------------------------------------------------
@@ -601,15 +486,6 @@ __device__ __forceinline__ void count_event(unsigned* ctr, bool bad) {
 }
 
 // ---------------------------------------------------------------------------------
-// out index o -> class segment
-__device__ __forceinline__ int seg_of(const int* seg_out_base, int n_seg, int total, int o) {
-  int c = 0;
-  for (int s = 1; s < n_seg; ++s)
-    if (o >= seg_out_base[s]) c = s;
-  (void)total;
-  return c;
-}
-
 __global__ __launch_bounds__(kB) void k_dyn_finish(DynFinishArgs a) {
   const long long o = (long long)blockIdx.x * kB + threadIdx.x;
   if (a.gmax_reset && o < a.F) a.gmax_reset[o] = ord_enc(-INFINITY);
@@ -621,23 +497,13 @@ __global__ __launch_bounds__(kB) void k_dyn_finish(DynFinishArgs a) {
     if (a.rows_host) a.rows_host[0] = r;
   }
   if (o >= a.n_out) return;
-  const int c = a.seg_out_base ? seg_of(a.seg_out_base, a.n_seg, (int)a.n_out, (int)o) : 0;
+  const int c = a.seg_out_base ? seg_of(a.seg_out_base, a.n_seg, o) : 0;
   const long long pos = (a.seg_pos_begin ? a.seg_pos_begin[c] : 0) + (o - (a.seg_out_base ? a.seg_out_base[c] : 0));
   const long long p = a.perm ? a.perm[pos] : pos;
   long long r = o;                      // tile row holding this particle's GP outputs
-  if (a.slot) r = a.slot[(long long)c * a.P + (p / a.Pf) * a.Pf + a.anc[p]];
-  double q = 0.0;
-  const int np = a.n_parts[c];
-  for (int k = 0; k < np; ++k) q += a.qpart[(long long)k * a.ld_q + r];
-  // k(x*, x*) of the dynamics kernel without noise: 1 + [x,1] diag(c^2) [x,1]^T (gpmdm.py:1100)
+  if (a.slot) r = a.slot[dedup_key(a.P, a.Pf, c, p, a.anc[p])];
   const int d = a.d;
-  double kd = 0.0;
-  for (int j = 0; j < d; ++j) {
-    const double x = a.X[p * d + j];
-    kd = fma(a.lin_c2[j] * x, x, kd);
-  }
-  kd = 1.0 + (kd + a.lin_c2[d]);
-  const double vc = kd - q;
+  const double vc = dyn_vc(a.qpart, a.ld_q, a.n_parts[c], r, a.X + p * d, a.lin_c2, d);
   if (a.var_out) {                      // predictive map (map_x_dynamics_for_class)
     for (int j = 0; j < d; ++j) a.var_out[o * d + j] = vc * a.il2[j];
     return;
@@ -656,7 +522,7 @@ __global__ __launch_bounds__(kB) void k_dyn_finish(DynFinishArgs a) {
       const double u1 = u01_oo(r.x, r.y), u2 = u01_co(r.z, r.w);
       const double rr = sqrt(-2.0 * log(u1));
       double sn, cs;
-      sincos(6.283185307179586476925 * u2, &sn, &cs);
+      sincos(6.283185307179586476925 * u2, &sn, &cs);   // (Box-Muller; k_fc_finish has the same lines)
       e0 = rr * cs;
       e1 = rr * sn;
     }
@@ -712,7 +578,6 @@ __global__ __launch_bounds__(kB) void k_obs_finish(ObsFinishArgs a) {
 //   ll = -1/2 sum_j[(z_j - mu_j)^2 / var_j + log var_j] + sum_j(-log sqrt var_j) - D/2 ln(2pi)_f32
 //      = -1/2 S / vc - D log vc - sum_j log il2_j - D/2 ln(2pi)_f32
 // (the reference's double count of log var kept, gpmdm_pf.py:188-192).
-// (a device function: k_small_resample computes a deferred finish with the same code)
 __device__ __forceinline__ double obs_ll_value(const ObsFinishArgs& a, long long o, double& vc) {
   double Dn = a.D, sum_log_il2 = a.sum_log_il2, ll_const = a.ll_const;
   if (a.ftab) {
@@ -767,45 +632,32 @@ __device__ __forceinline__ double obs_ll_value(const ObsFinishArgs& a, long long
   return -0.5 * S / vc - Dn * log(vc) - sum_log_il2 - ll_const;
 }
 
-// the value a predictive filter keeps for particle pi (ObsFinishArgs::vc_out): the vc that
-// obs_ll_value formed, or NaN where it returned early (a masked bank's blacked-out filter)
-__device__ __forceinline__ double obs_vc_kept(const ObsFinishArgs& a, long long pi, double vc) {
-  return a.ftab && a.ftab[3 * (pi / a.Pf)] == 0.0 ? __longlong_as_double(0x7ff8000000000000ll) : vc;
+// The likelihood finish of output o (live: o < n_out; every thread of the wave calls it, for
+// the counters' ballots): ll stored at the output's particle, the vc a predictive filter keeps
+// (ObsFinishArgs::vc_out: the vc that obs_ll_value formed, or NaN where it returned early, a
+// masked bank's blacked-out filter), the health counters.  Returns ll (0 for a dead thread).
+__device__ __forceinline__ double obs_ll_step(const ObsFinishArgs& a, long long o, bool live) {
+  double vc = 1.0, llv = 0.0;
+  if (live) {
+    llv = obs_ll_value(a, o, vc);
+    const long long pi = a.own ? a.own[a.ll_offset + o] : a.ll_offset + o;
+    a.ll[pi] = llv;
+    if (a.vc_out)
+      a.vc_out[pi] = a.ftab && a.ftab[3 * (pi / a.Pf)] == 0.0 ? __longlong_as_double(0x7ff8000000000000ll) : vc;
+  }
+  if (a.health) {
+    count_event(a.health + kHealthObsVar, live && !(vc > 0.0));
+    count_event(a.health + kHealthObsLL, live && !isfinite(llv));
+  }
+  return llv;
 }
 
 __global__ __launch_bounds__(kB) void k_obs_ll(ObsFinishArgs a) {
   const long long o = (long long)blockIdx.x * kB + threadIdx.x;
-  unsigned long long key = 0;            // below ord_enc of any double
-  if (o < a.n_out) {
-    double vc;
-    const double llv = obs_ll_value(a, o, vc);
-    const long long pi = a.own ? a.own[a.ll_offset + o] : a.ll_offset + o;
-    a.ll[pi] = llv;
-    if (a.vc_out) a.vc_out[pi] = obs_vc_kept(a, pi, vc);
-    if (a.health) {
-      count_event(a.health + kHealthObsVar, !(vc > 0.0));
-      count_event(a.health + kHealthObsLL, !isfinite(llv));
-    }
-    key = ord_enc(fmax(-INFINITY, llv));  // k_norm_max's value set: NaN ignored
-  }
-  if (a.bmax) {
-    // the block's maximum as an integer key: the max of a set in ord_enc's total order
-    // does not depend on how the set is split, so k_norm_exp_scan's max over the block
-    // maxima is k_norm_max's atomicMax result exactly
-    __shared__ unsigned long long wk[kB / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const unsigned long long y = __shfl_xor(key, off);
-      key = y > key ? y : key;
-    }
-    if ((threadIdx.x & 63) == 0) wk[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned long long m = wk[0];
-      for (int i = 1; i < kB / 64; ++i) m = wk[i] > m ? wk[i] : m;
-      a.bmax[blockIdx.x] = m;
-    }
-  }
+  const bool live = o < a.n_out;
+  const double llv = obs_ll_step(a, o, live);
+  // k_norm_max's value set: NaN ignored; a dead thread's key is below ord_enc of any double
+  if (a.bmax) block_max_key_store<kB / 64>(live ? ord_enc(fmax(-INFINITY, llv)) : 0ull, a.bmax);
 }
 
 // ---------------------------------------------------------------------------------
@@ -831,7 +683,7 @@ __global__ __launch_bounds__(kB) void k_norm_max(NormArgs a) {
 __global__ __launch_bounds__(kB) void k_norm_exp_scan(NormArgs a) {
   __shared__ double wsum[kB / 64];
   __shared__ unsigned long long wk[kB / 64];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const long long f = blockIdx.y;
   const long long p = (long long)blockIdx.x * kB + tid;
   double M;
@@ -841,15 +693,7 @@ __global__ __launch_bounds__(kB) void k_norm_exp_scan(NormArgs a) {
     unsigned long long key = 0;
     const int nk = a.nbmax ? a.nbmax : a.nb;
     for (int i = tid; i < nk; i += kB) key = a.bmax[i] > key ? a.bmax[i] : key;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const unsigned long long y = __shfl_xor(key, off);
-      key = y > key ? y : key;
-    }
-    if (lane == 0) wk[w] = key;
-    __syncthreads();
-    key = wk[0];
-    for (int i = 1; i < kB / 64; ++i) key = wk[i] > key ? wk[i] : key;
+    key = block_max_key<kB / 64>(key, wk);
     if (blockIdx.x == 0 && tid == 0) a.gmax[f] = key;
     M = ord_dec(key);
   } else {
@@ -857,52 +701,19 @@ __global__ __launch_bounds__(kB) void k_norm_exp_scan(NormArgs a) {
   }
   const double e = p < a.P ? exp(a.ll[f * a.P + p] - M) : 0.0;
   if (p < a.P) a.e[f * a.P + p] = e;
-  double x = e;                               // wave inclusive scan
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const double y = __shfl_up(x, off);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) wsum[w] = x;
-  __syncthreads();
-  double base = 0.0;
-  for (int v = 0; v < w; ++v) base += wsum[v];
-  x += base;
+  const double x = block_inclusive_scan(e, 0.0, OpSum(), wsum, tid >> 6);
   if (p < a.P) a.local[f * a.P + p] = x;
   if (tid == kB - 1) a.blocksum[f * a.nb + blockIdx.x] = x;
 }
 
-// One workgroup per filter: exclusive scan of block sums, total S.
+// One workgroup per filter: exclusive scan of block sums, total S.  The Hillis-Steele form:
+// k_small_resample reproduces its association.
 __global__ __launch_bounds__(1024) void k_norm_total(NormArgs a) {
-  __shared__ double part[1024];
-  const int tid = threadIdx.x;
-  const int nb = a.nb;
   const long long f = blockIdx.x;
-  const double* blocksum = a.blocksum + f * nb;
-  double* blockoff = a.blockoff + f * nb;
-  const int chunk = (nb + 1023) / 1024;
-  double s = 0.0;
-  for (int i = 0; i < chunk; ++i) {
-    const int b = tid * chunk + i;
-    if (b < nb) s += blocksum[b];
-  }
-  part[tid] = s;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const double v = tid >= off ? part[tid - off] : 0.0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  double run = tid ? part[tid - 1] : 0.0;
-  for (int i = 0; i < chunk; ++i) {
-    const int b = tid * chunk + i;
-    if (b < nb) {
-      blockoff[b] = run;
-      run += blocksum[b];
-    }
-  }
-  if (tid == 1023) a.total[f] = part[1023];
+  const double S =
+      chunked1024_exclusive_scan(a.blocksum + f * a.nb, a.blockoff + f * a.nb, 1, a.nb, 0.0, OpSum(),
+                                 [](double x, double* t) { return block1024_exclusive_scan_hs(x, 0.0, OpSum(), t); });
+  if (threadIdx.x == 1023) a.total[f] = S;
 }
 
 // The normalised CDF of filter f at particle i: k_norm_exp_scan's block-local inclusive scan
@@ -922,17 +733,30 @@ __global__ __launch_bounds__(1024) void k_norm_total(NormArgs a) {
 // do not decrease with u, with uniforms placed on the CDF's values at every block boundary;
 // with weights in {0, 1} every sum is an integer, the CDF is monotone and the ancestors are
 // np.searchsorted's exactly.
+__device__ __forceinline__ double cdf_value(double boff, double local, double S, bool last) {
+  return last ? 1.0 : (boff + local) / S;
+}
 struct CdfView {
   const double* boff;
   const double* local;
   double S;
   long long P;
   __device__ __forceinline__ double operator[](long long i) const {
-    return i == P - 1 ? 1.0 : (boff[i / kB] + local[i]) / S;
+    return cdf_value(boff[i / kB], local[i], S, i == P - 1);
   }
 };
 __device__ __forceinline__ CdfView cdf_view(const ResampleArgs& a, long long f) {
   return CdfView{a.blockoff + f * a.nb, a.local + f * a.P, a.total[f], a.P};
+}
+// First index of [lo, hi) with cum >= u, hi if none (torch's searchsorted); cum: a CdfView, or
+// the CDF's values in LDS.
+template <class Cdf>
+__device__ __forceinline__ long long cdf_search(const Cdf& cum, double u, long long lo, long long hi) {
+  while (hi - lo > 0) {
+    const long long mid = lo + (hi - lo) / 2;
+    if (cum[mid] < u) lo = mid + 1; else hi = mid;
+  }
+  return lo;
 }
 
 // One thread per output slot s: inverse-CDF search, gather, read-out partials.
@@ -981,7 +805,7 @@ __global__ __launch_bounds__(kB) void k_guide(ResampleArgs a) {
   }
   const long long A0 = __shfl(L, 0), A1 = __shfl(L, 32);
   const double t = (double)b / (double)a.GB;
-  long long lo = A0, hi = A1;                          // this lane's answer is in [A0, A1]
+  long long lo = A0;                                   // this lane's answer is in [A0, A1]
   if (A1 - A0 <= 64) {
     // the range's CDF values in registers, one per lane; per lane a binary search over them
     const double v = A0 + lane < A1 ? cum[A0 + lane] : 0.0;
@@ -995,10 +819,7 @@ __global__ __launch_bounds__(kB) void k_guide(ResampleArgs a) {
     }
     lo = A0 + l;
   } else {
-    while (hi - lo > 0) {
-      const long long mid = lo + (hi - lo) / 2;
-      if (cum[mid] < t) lo = mid + 1; else hi = mid;
-    }
+    lo = cdf_search(cum, t, A0, A1);
   }
   if (b < nb) a.guide[f * nb + b] = (int)lo;
 }
@@ -1043,56 +864,63 @@ __global__ __launch_bounds__(kB) void k_sys_marks(ResampleArgs a) {
 // block-local inclusive max-scan of the marks (in place) and the block maxima
 __global__ __launch_bounds__(kB) void k_sys_scan(ResampleArgs a) {
   __shared__ int wmax[kB / 64];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const long long f = blockIdx.y;
   const long long s = (long long)blockIdx.x * kB + tid;
-  int x = s < a.P ? a.sys_mark[f * a.P + s] : -1;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(x, off);
-    if (lane >= off) x = max(x, y);
-  }
-  if (lane == 63) wmax[w] = x;
-  __syncthreads();
-  for (int v = 0; v < w; ++v) x = max(x, wmax[v]);
+  const int x = block_inclusive_scan(s < a.P ? a.sys_mark[f * a.P + s] : -1, -1, OpMax(), wmax, tid >> 6);
   if (s < a.P) a.sys_mark[f * a.P + s] = x;
   if (tid == kB - 1) a.sys_block[f * a.nb + blockIdx.x] = x;
 }
 
 // one workgroup per filter: exclusive max-scan of the block maxima (in place)
 __global__ __launch_bounds__(1024) void k_sys_blocks(ResampleArgs a) {
-  __shared__ int part[1024];
-  const int tid = threadIdx.x;
-  const long long f = blockIdx.x;
-  int* blk = a.sys_block + f * a.nb;
-  const int chunk = (a.nb + 1023) / 1024;
-  int mx = -1;
-  for (int i = 0; i < chunk; ++i) {
-    const int b = tid * chunk + i;
-    if (b < a.nb) mx = max(mx, blk[b]);
-  }
-  part[tid] = mx;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int v = tid >= off ? part[tid - off] : -1;
-    __syncthreads();
-    part[tid] = max(part[tid], v);
-    __syncthreads();
-  }
-  int run = tid ? part[tid - 1] : -1;
-  for (int i = 0; i < chunk; ++i) {
-    const int b = tid * chunk + i;
-    if (b < a.nb) {
-      const int v = blk[b];
-      blk[b] = run;
-      run = max(run, v);
+  int* blk = a.sys_block + (long long)blockIdx.x * a.nb;
+  chunked1024_exclusive_scan(blk, blk, 1, a.nb, -1, OpMax(),
+                             [](int x, int* t) { return block1024_exclusive_scan_hs(x, -1, OpMax(), t); });
+}
+
+// The uniform of slot s of filter f; u_replay: the replay's uniform for the slot where a.U is
+// set (U[0] for systematic resampling, else U[s]), loaded by the caller.
+__device__ __forceinline__ double resample_uniform(const ResampleArgs& a, long long f, long long s, uint2 key,
+                                                   double u_replay) {
+  if (a.systematic) return sys_u(s, a.U ? u_replay : sys_u0(a, f), a.P);
+  if (a.U) return u_replay;
+  const uint4 r = philox4x32_10(make_uint4((unsigned)s, a.frame, kStreamResample, 0u), key);
+  return u01_co(r.x, r.y);
+}
+
+// The read-out terms of slot s (pre-resample ll / e at slot s; M = max ll, S = sum e): e2 the
+// unnormalised weight of the likelihood read-outs, wv the normalised weight of the state mean.
+__device__ __forceinline__ void readout_terms(double llv, double M, double e, double S, double& e2, double& wv) {
+  const double lw = llv - M;
+  e2 = exp((llv + lw) - M);                  // ll + log_w - max(ll + log_w); that max is M
+  wv = e / S;
+}
+// One block's sums of the nq = C + 1 + d read-out quantities of its slots (act: a live slot of
+// post-resample class cnew and state xs): wave sums into red (the block's, LDS), then for thread
+// t < nq of the block the four waves of quantity t in order (other threads: 0).  Contains a barrier.
+__device__ __forceinline__ double readout_block_sum(bool act, int cnew, double e2, double wv, const double* xs, int C,
+                                                    int nq, BlockGeo g, double (*red)[kMaxReadout]) {
+  for (int k = 0; k < nq; ++k) {
+    double v = 0.0;
+    if (act) {
+      if (k < C) v = (cnew == k) ? e2 : 0.0;
+      else if (k == C) v = e2;
+      else v = xs[k - C - 1] * wv;
     }
+    v = wave_sum(v);
+    if ((g.t & 63) == 0) red[g.wq][k] = v;
   }
+  __syncthreads();
+  double t = 0.0;
+  if (g.t < nq)
+    for (int v = 0; v < kB / 64; ++v) t += red[v][g.t];
+  return t;
 }
 
 __global__ __launch_bounds__(kB) void k_resample(ResampleArgs a) {
   __shared__ double red[kB / 64][kMaxReadout];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const long long f = blockIdx.y;
   const long long s = (long long)blockIdx.x * kB + tid;   // slot within filter f
   const long long g0 = f * a.P;                            // filter f's first particle
@@ -1110,16 +938,8 @@ __global__ __launch_bounds__(kB) void k_resample(ResampleArgs a) {
     } else if (a.sys_mark) {                                // systematic by scan
       idx = max(a.sys_mark[g0 + s], a.sys_block[f * a.nb + blockIdx.x]);
     } else {
-      double u;
-      if (a.systematic) {                    // (search form; the filter resamples by scan)
-        u = sys_u(s, sys_u0(a, f), a.P);
-      } else if (a.U) {
-        u = a.U[s];
-      } else {
-        const uint4 r = philox4x32_10(make_uint4((unsigned)s, a.frame, kStreamResample, 0u), key);
-        u = u01_co(r.x, r.y);
-      }
-      const CdfView cum = cdf_view(a, f);
+      // (systematic: the search form; the filter resamples by scan)
+      const double u = resample_uniform(a, f, s, key, a.U ? a.U[a.systematic ? 0 : s] : 0.0);
       // first index with cum >= u (torch's searchsorted), searched between two guide
       // entries that bracket it: t_lo = (q0 - 1) / GB <= u and t_hi = (q0 + 2) / GB > u for
       // q0 = floor(u GB) whatever its rounding, so the result is exactly that of a search
@@ -1131,11 +951,7 @@ __global__ __launch_bounds__(kB) void k_resample(ResampleArgs a) {
         lo = gd[q0 - 1 > 0 ? q0 - 1 : 0];
         hi = gd[q0 + 2 < a.GB + 2 ? q0 + 2 : a.GB + 2];
       }
-      while (hi - lo > 0) {
-        const long long mid = lo + (hi - lo) / 2;
-        if (cum[mid] < u) lo = mid + 1; else hi = mid;
-      }
-      idx = lo;
+      idx = cdf_search(cdf_view(a, f), u, lo, hi);
     }
     if (a.rows) {                 // the exchanged row of particle idx, read in place
       const double* row = a.rows + (a.rows_inv ? (long long)a.rows_inv[g0 + idx] : g0 + idx) * a.rows_w;
@@ -1150,17 +966,14 @@ __global__ __launch_bounds__(kB) void k_resample(ResampleArgs a) {
       a.cls_dst[g0 + s] = cnew;
     }
     // read-outs: post-resample class/state at slot s, pre-resample ll/log_w at slot s
-    const double M = ord_dec(a.gmax[f]);
-    const double llv = a.ll[g0 + s];
-    const double lw = llv - M;
-    e2 = exp((llv + lw) - M);                  // ll + log_w - max(ll + log_w); that max is M
-    wv = a.e[g0 + s] / a.total[f];
+    readout_terms(a.ll[g0 + s], ord_dec(a.gmax[f]), a.e[g0 + s], a.total[f], e2, wv);
   }
   if (!a.identity) {
     // The wave's 64 new states are one contiguous run of X_dst: lane l stores its elements
     // l, l + 64, ... of that run (8-byte stores, each instruction one contiguous 512 bytes)
     // from the source rows it finds through the owning lanes' pointers -- rows this wave has
     // just read.  Per-lane stores of d doubles at stride 8 d bytes ran at ~1 TB/s.
+    // (k_small_resample keeps the per-lane rows: at most 1024 of them, latency-bound.)
     const long long s0 = s - lane;                         // the wave's first slot
     const long long nv = a.P - s0 < 64 ? a.P - s0 : 64;   // its slots in range (wave-uniform)
     const long long n = nv * d;
@@ -1170,33 +983,17 @@ __global__ __launch_bounds__(kB) void k_resample(ResampleArgs a) {
       if (e < n) a.X_dst[(g0 + s0) * d + e] = src[i2];
     }
   }
-  for (int k = 0; k < nq; ++k) {
-    double v = 0.0;
-    if (act) {
-      if (k < C) v = (cnew == k) ? e2 : 0.0;
-      else if (k == C) v = e2;
-      else v = xs[k - C - 1] * wv;
-    }
-    v = wave_sum(v);
-    if (lane == 0) red[w][k] = v;
-  }
-  __syncthreads();
-  if (tid < nq) {
-    double t = 0.0;
-    for (int v = 0; v < kB / 64; ++v) t += red[v][tid];
-    a.partials[(f * a.nb + blockIdx.x) * nq + tid] = t;
-  }
+  const double t = readout_block_sum(act, cnew, e2, wv, xs, C, nq, grid_block(), red);
+  if (tid < nq) a.partials[(f * a.nb + blockIdx.x) * nq + tid] = t;
 }
 
 // The all-gathered {ll} column (rows in position order: row r holds particle own[r]) into
 // particle order, with each kRowsLL-particle block's maximum as an ord_enc key: the
 // normaliser's maximum (gpmdm_pf.py:200) without k_norm_max, as k_obs_ll gives it to a
-// single rank.  The maximum of a set in ord_enc's total order does not depend on how the
-// set is split, so it is k_norm_max's result exactly.
+// single rank.
 constexpr int kRowsLLPer = 8;
 constexpr long long kRowsLL = (long long)kRowsLLPer * kB;
 __global__ __launch_bounds__(kB) void k_rows_ll(RowsLLArgs a) {
-  __shared__ unsigned long long wk[kB / 64];
   unsigned long long key = 0;            // below ord_enc of any double
 #pragma unroll
   for (int k = 0; k < kRowsLLPer; ++k) {
@@ -1208,18 +1005,7 @@ __global__ __launch_bounds__(kB) void k_rows_ll(RowsLLArgs a) {
       key = kk > key ? kk : key;
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long y = __shfl_xor(key, off);
-    key = y > key ? y : key;
-  }
-  if ((threadIdx.x & 63) == 0) wk[threadIdx.x >> 6] = key;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long m = wk[0];
-    for (int i = 1; i < kB / 64; ++i) m = wk[i] > m ? wk[i] : m;
-    a.bmax[blockIdx.x] = m;
-  }
+  block_max_key_store<kB / 64>(key, a.bmax);
 }
 
 // The read-out is in mapped host memory: publish its sequence number after it, so the host
@@ -1243,24 +1029,25 @@ __device__ inline void publish_readout(const ResampleArgs& a, long long f, int t
   if (tid == 0) publish_seq(a.seq_host + f, a.seq);
 }
 
-__global__ __launch_bounds__(1024) void k_readout(ResampleArgs a) {
+// One 1024-thread workgroup: filter f's read-out from its nb blocks' partial sums (row b at
+// partials + b * ld: the buffer, or its LDS mirror), stored to readout and readout_host.
+// Returns whether this thread stored a value.  Contains barriers.
+__device__ __forceinline__ bool readout_values(const ResampleArgs& a, long long f, const double* partials, int ld,
+                                               int nb) {
   __shared__ double red[8][16];
   __shared__ double tot[kMaxReadout];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int nq = a.C + 1 + a.d;
-  const long long f = blockIdx.x;
-  const double* partials = a.partials + f * a.nb * nq;
-  double* readout = a.readout + f * (a.C + a.d + 1);
   // eight read-out quantities per pass over the partials (every thread's loads in flight
   // together; per quantity the same thread-strided order as one quantity at a time)
   for (int k0 = 0; k0 < nq; k0 += 8) {
     double s[8];
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) s[kk] = 0.0;
-    for (long long b = tid; b < a.nb; b += 1024)
+    for (long long b = tid; b < nb; b += 1024)
 #pragma unroll
       for (int kk = 0; kk < 8; ++kk)
-        if (k0 + kk < nq) s[kk] += partials[b * nq + k0 + kk];
+        if (k0 + kk < nq) s[kk] += partials[b * ld + k0 + kk];
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) {
       const double v = wave_sum(s[kk]);
@@ -1288,75 +1075,66 @@ __global__ __launch_bounds__(1024) void k_readout(ResampleArgs a) {
     } else {
       v = tot[a.C];                                      // log_likelihood()
     }
-    readout[tid] = v;
+    a.readout[f * nro + tid] = v;
     if (a.readout_host) a.readout_host[f * nro + tid] = v;
   }
+  return tid < nro;
+}
+
+__global__ __launch_bounds__(1024) void k_readout(ResampleArgs a) {
+  const int tid = threadIdx.x;
+  const long long f = blockIdx.x;
+  const int nq = a.C + 1 + a.d;
+  const bool ro = readout_values(a, f, a.partials + f * a.nb * nq, nq, a.nb);
   // the AUTO cutoff's counters of this frame, one per lane (8-byte stores: the ISA guard)
   const bool cst = a.cut_stats && f == 0 && tid < 2;
   if (cst) {
     a.cut_stats_host[tid] = a.cut_stats[tid];
     a.cut_stats[tid] = 0;
   }
-  publish_readout(a, f, tid, tid < nro || cst);
+  publish_readout(a, f, tid, ro || cst);
 }
 
 
 // ---------------------------------------------------------------------------------
 // Small filters (P <= kSmallP per filter, no guide table): one 1024-thread workgroup per
 // filter runs normalise + CDF + resample + read-out in one launch instead of six -- at the
-// notebook's P = 100 each launch of the multi-kernel path costs more than its work.  The
-// arithmetic is the multi-kernel path's, association for association: the 256-thread
-// blocks of k_norm_exp_scan / k_resample (and cdf_view's 256-particle blocks) are the
-// workgroup's four 256-thread quarters (block b = waves 4b .. 4b+3, so every wave-level scan /
-// sum sees the same lanes),
-// k_norm_total / k_readout run as they are, and intermediates go through the same buffers;
-// the max is exact in any order.  Systematic resampling takes the search form, whose indices
-// the scan form reproduces exactly (k_sys_marks).  Results are bitwise those of the
-// multi-kernel path (tests/test_gpu_small_path.py).
+// notebook's P = 100 each launch of the multi-kernel path costs more than its work.  The steps
+// are the multi-kernel path's own device functions (obs_ll_step, block_inclusive_scan,
+// cdf_value, resample_uniform, cdf_search, readout_terms, readout_block_sum, readout_values),
+// called with the workgroup's quarters as the 256-thread blocks of k_norm_exp_scan /
+// k_resample and cdf_view, and with LDS mirrors (M, block sums and offsets, S, the CDF, the
+// read-out partials) where that path reads a buffer back; the buffers are still written for
+// their other readers.  Its own: the maximum (exact in any order); k_norm_total's scan,
+// emulated over four slots (below); the early load of the replay uniforms; per-lane X_dst rows
+// (see k_resample).  Systematic resampling takes the search form, whose indices the scan form
+// reproduces exactly (k_sys_marks).  Results are bitwise those of the multi-kernel path
+// (tests/test_gpu_small_path.py).
 constexpr long long kSmallP = 1024;
 
 __global__ __launch_bounds__(1024) void k_small_resample(NormArgs na, ResampleArgs a) {
   __shared__ double mx[16];
   __shared__ double wsum[4][4];
-  // the values the multi-kernel path reads back from its buffers, kept here as written
-  // (the buffers are still written for their other readers): M, block sums / offsets, S,
-  // the read-out partials
   __shared__ double Msh, Ssh, bsum[4], boff[4];
-  __shared__ double psh[4][kMaxReadout];
+  __shared__ double psh[4][kMaxReadout];              // partials
   __shared__ double cum_s[kSmallP];
   __shared__ double red[4][4][kMaxReadout];
-  __shared__ double rred[8][16];
-  __shared__ double tot[kMaxReadout];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int b = tid >> 8, wq = w & 3;                 // block of the multi-kernel path, its wave
+  const BlockGeo g = quarter_block();
   const long long f = blockIdx.x;
   const long long P = na.P;
   const int nb = na.nb;
-  const long long p = tid;                            // = b * 256 + (tid & 255)
+  const long long p = tid;                            // = g.b * 256 + g.t
   const long long g0 = f * P;
+  const bool act = p < P;
   // the replay uniforms (host-mapped for small filters: a PCIe round trip) are loaded
   // here, ahead of the phases before the search, so their latency overlaps them
-  const double u_pre = (a.U && !a.identity && p < P) ? a.U[a.systematic ? 0 : p] : 0.0;
-  double llp;
-  if (na.obs_pending) {
-    // ---- k_obs_ll (deferred by the single-shard filter's weigh step): out index g0 + p ----
-    double vc = 1.0, llv = 0.0;
-    if (p < P) {
-      llv = obs_ll_value(na.obs, g0 + p, vc);
-      na.obs.ll[g0 + p] = llv;
-      if (na.obs.vc_out) na.obs.vc_out[g0 + p] = obs_vc_kept(na.obs, g0 + p, vc);
-    }
-    if (na.obs.health) {
-      count_event(na.obs.health + kHealthObsVar, p < P && !(vc > 0.0));
-      count_event(na.obs.health + kHealthObsLL, p < P && !isfinite(llv));
-    }
-    llp = llv;
-  } else {
-    llp = p < P ? na.ll[g0 + p] : 0.0;
-  }
+  const double u_pre = (a.U && !a.identity && act) ? a.U[a.systematic ? 0 : p] : 0.0;
+  // ---- k_obs_ll (deferred by the single-shard filter's weigh step): out index g0 + p ----
+  const double llp = na.obs_pending ? obs_ll_step(na.obs, g0 + p, act) : (act ? na.ll[g0 + p] : 0.0);
   // ---- k_norm_max: the largest ll (NaN ignored, as fmax does) ----
   {
-    double v = p < P ? llp : -INFINITY;
+    double v = act ? llp : -INFINITY;
     v = fmax(-INFINITY, v);
     v = wave_max(v);
     if (lane == 0) mx[w] = v;
@@ -1371,27 +1149,13 @@ __global__ __launch_bounds__(1024) void k_small_resample(NormArgs na, ResampleAr
   }
   const double M = Msh;
   // ---- k_norm_exp_scan ----
-  const double e = p < P ? exp(llp - M) : 0.0;
-  if (p < P) na.e[g0 + p] = e;
-  double e_incl;
-  {
-    double x = e;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const double y = __shfl_up(x, off);
-      if (lane >= off) x += y;
-    }
-    if (lane == 63) wsum[b][wq] = x;
-    __syncthreads();
-    double base = 0.0;
-    for (int v = 0; v < wq; ++v) base += wsum[b][v];
-    x += base;
-    e_incl = x;
-    if (p < P) na.local[g0 + p] = x;
-    if ((tid & 255) == 255 && b < nb) {
-      na.blocksum[f * nb + b] = x;
-      bsum[b] = x;
-    }
+  const double e = act ? exp(llp - M) : 0.0;
+  if (act) na.e[g0 + p] = e;
+  const double e_incl = block_inclusive_scan(e, 0.0, OpSum(), wsum[g.b], g.wq);
+  if (act) na.local[g0 + p] = e_incl;
+  if (g.t == kB - 1 && g.b < nb) {
+    na.blocksum[f * nb + g.b] = e_incl;
+    bsum[g.b] = e_incl;
   }
   __syncthreads();
   // ---- k_norm_total ----
@@ -1411,105 +1175,39 @@ __global__ __launch_bounds__(1024) void k_small_resample(NormArgs na, ResampleAr
   const double S = Ssh;
   if (tid < nb) na.blockoff[f * nb + tid] = boff[tid];      // one 8-byte store per lane
   if (tid == 0) na.total[f] = S;
-  // ---- the CDF (cdf_view's expression) ----
-  if (p < P) cum_s[p] = p == P - 1 ? 1.0 : (boff[b] + e_incl) / S;
+  if (act) cum_s[p] = cdf_value(boff[g.b], e_incl, S, p == P - 1);
   __syncthreads();
   // ---- k_resample (slot s = p) ----
-  const uint2 key = filter_key(a.seed_lo, a.seed_hi, f);
   const int C = a.C, d = a.d, nq = C + 1 + d;
-  const bool act = p < P;
   long long idx = 0;
   int cnew = -1;
+  const double* xs = nullptr;
   double e2 = 0.0, wv = 0.0;
   if (act) {
     if (a.identity) {
       idx = p;
     } else {
-      double u;
-      if (a.systematic) {
-        u = sys_u(p, a.U ? u_pre : sys_u0(a, f), P);
-      } else if (a.U) {
-        u = u_pre;
-      } else {
-        const uint4 r = philox4x32_10(make_uint4((unsigned)p, a.frame, kStreamResample, 0u), key);
-        u = u01_co(r.x, r.y);
-      }
-      long long lo = 0, hi = P;
-      while (hi - lo > 0) {
-        const long long mid = lo + (hi - lo) / 2;
-        if (cum_s[mid] < u) lo = mid + 1; else hi = mid;
-      }
-      idx = lo;
+      const double u = resample_uniform(a, f, p, filter_key(a.seed_lo, a.seed_hi, f), u_pre);
+      idx = cdf_search(cum_s, u, 0, P);
     }
     cnew = a.cls_src[g0 + idx];
+    xs = a.X_src + (g0 + idx) * d;
     if (!a.identity) {
       a.ridx[g0 + p] = (int)idx;
       a.cls_dst[g0 + p] = cnew;
       if (a.cls_host) a.cls_host[g0 + p] = cnew;
-      for (int j = 0; j < d; ++j) a.X_dst[(g0 + p) * d + j] = a.X_src[(g0 + idx) * d + j];
+      for (int j = 0; j < d; ++j) a.X_dst[(g0 + p) * d + j] = xs[j];
     }
-    const double llv = llp;
-    const double lw = llv - M;
-    e2 = exp((llv + lw) - M);
-    wv = e / S;
+    readout_terms(llp, M, e, S, e2, wv);
   }
-  for (int k = 0; k < nq; ++k) {
-    double v = 0.0;
-    if (act) {
-      if (k < C) v = (cnew == k) ? e2 : 0.0;
-      else if (k == C) v = e2;
-      else v = a.X_src[(g0 + idx) * d + (k - C - 1)] * wv;
-    }
-    v = wave_sum(v);
-    if (lane == 0) red[b][wq][k] = v;
-  }
-  __syncthreads();
-  if ((tid & 255) < nq && b < nb) {
-    const int k = tid & 255;
-    double t = 0.0;
-    for (int v = 0; v < 4; ++v) t += red[b][v][k];
-    a.partials[(f * nb + b) * nq + k] = t;
-    psh[b][k] = t;
+  const double t = readout_block_sum(act, cnew, e2, wv, xs, C, nq, g, red[g.b]);
+  if (g.t < nq && g.b < nb) {
+    a.partials[(f * nb + g.b) * nq + g.t] = t;
+    psh[g.b][g.t] = t;
   }
   __syncthreads();
   // ---- k_readout ----
-  double* readout = a.readout + f * (C + d + 1);
-  for (int k0 = 0; k0 < nq; k0 += 8) {
-    double sv[8];
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) sv[kk] = 0.0;
-    if (tid < nb)
-#pragma unroll
-      for (int kk = 0; kk < 8; ++kk)
-        if (k0 + kk < nq) sv[kk] += psh[tid][k0 + kk];
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-      const double v = wave_sum(sv[kk]);
-      if (lane == 0) rred[kk][w] = v;
-    }
-    __syncthreads();
-    if (tid < 8 && k0 + tid < nq) {
-      double t = 0.0;
-      for (int v = 0; v < 16; ++v) t += rred[tid][v];
-      tot[k0 + tid] = t;
-    }
-    __syncthreads();
-  }
-  const int nro = C + d + 1;
-  if (tid < nro) {
-    double v;
-    if (tid < C) {
-      double cl = 0.0;
-      for (int c = 0; c < C; ++c) cl += tot[c];
-      v = tot[tid] / cl;
-    } else if (tid < C + d) {
-      v = tot[tid + 1];
-    } else {
-      v = tot[C];
-    }
-    readout[tid] = v;
-    if (a.readout_host) a.readout_host[f * nro + tid] = v;
-  }
+  readout_values(a, f, &psh[0][0], kMaxReadout, nb);
   publish_readout(a, f, tid, true);   // (cls_host: any slot's thread)
 }
 
@@ -1596,6 +1294,12 @@ __global__ void k_seg_table(int* t, int n, int tiles) {
 // ---------------------------------------------------------------------------------
 static inline unsigned nblk(long long n, int b) { return (unsigned)((n + b - 1) / b); }
 
+// GPMDM_NO_SMALL_PATH=1 forces the multi-kernel path (the reference of tests/test_gpu_small_path.py)
+static bool small_path_enabled() {
+  static const bool on = std::getenv("GPMDM_NO_SMALL_PATH") == nullptr;
+  return on;
+}
+
 void launch_seg_table(int* t, int n, int tiles, hipStream_t s) {
   hipLaunchKernelGGL(k_seg_table, dim3(1), dim3(64), 0, s, t, n, tiles);
 }
@@ -1609,7 +1313,7 @@ void launch_predict_mean(const int* perm, const double* mu, double* mu_p, double
   hipLaunchKernelGGL(k_predict_mean, dim3((unsigned)F), dim3(kB), 0, s, mu_p, out, Pf, d);
 }
 
-void launch_switch(const SwitchArgs& a, hipStream_t s) {
+static void launch_switch(const SwitchArgs& a, hipStream_t s) {
   if (a.own)
     hipLaunchKernelGGL(k_switch<true>, dim3(nblk(a.n > 0 ? a.n : 1, kB)), dim3(kB), 0, s, a);
   else
@@ -1624,15 +1328,24 @@ void launch_group(const GroupArgs& a, hipStream_t s) {
   else
     hipLaunchKernelGGL(k_group<false>, dim3(nblk(a.n > 0 ? a.n : 1, kB)), dim3(kB), 0, s, a);
 }
+static void launch_lead(const LeadArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(k_lead_flags, dim3((unsigned)a.nb), dim3(kB), 0, s, a);
+  if (a.nb <= kMaxLeadBlocks) {
+    hipLaunchKernelGGL(k_lead_tables_compact, dim3((unsigned)a.nb), dim3(kB), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(k_lead_tables, dim3(1), dim3(1024), 0, s, a);
+    hipLaunchKernelGGL(k_lead_compact, dim3((unsigned)a.nb), dim3(kB), 0, s, a);
+  }
+}
 // switch + class scan + grouping (+ leader compaction with `la`): one launch for a small
 // single-shard filter (k_small_switch, the same tables), the multi-kernel path otherwise.
 // The owner preset of the leader election is part of either path.
 bool launch_switch_group(const SwitchArgs& sa, const ScanArgs& sc, const GroupArgs& ga, const LeadArgs* la,
                          bool owner_preset, hipStream_t s) {
-  static const bool no_small = std::getenv("GPMDM_NO_SMALL_PATH") != nullptr;
-  if (!no_small && sa.P <= kSmallSwitchP && sa.n == sa.P && sa.base == 0 && !sa.own && sa.n > 0 &&
+  if (small_path_enabled() && sa.P <= kSmallSwitchP && sa.n == sa.P && sa.base == 0 && !sa.own && sa.n > 0 &&
       (la == nullptr) == (sa.owner == nullptr) && (la == nullptr || la->npos == sa.P)) {
     LeadArgs l = la ? *la : LeadArgs{};
+    l.owner_reset = nullptr;             // the kernel presets the whole table itself
     hipLaunchKernelGGL(k_small_switch, dim3(1), dim3(1024), 0, s, sa, sc, ga, l, la ? 1 : 0);
     return true;
   }
@@ -1642,15 +1355,6 @@ bool launch_switch_group(const SwitchArgs& sa, const ScanArgs& sc, const GroupAr
   launch_group(ga, s);
   if (la) launch_lead(*la, s);
   return false;
-}
-void launch_lead(const LeadArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_lead_flags, dim3((unsigned)a.nb), dim3(kB), 0, s, a);
-  if (a.nb <= kMaxLeadBlocks) {
-    hipLaunchKernelGGL(k_lead_tables_compact, dim3((unsigned)a.nb), dim3(kB), 0, s, a);
-  } else {
-    hipLaunchKernelGGL(k_lead_tables, dim3(1), dim3(1024), 0, s, a);
-    hipLaunchKernelGGL(k_lead_compact, dim3((unsigned)a.nb), dim3(kB), 0, s, a);
-  }
 }
 void launch_dyn_finish(const DynFinishArgs& a, hipStream_t s) {
   if (a.n_out > 0) hipLaunchKernelGGL(k_dyn_finish, dim3(nblk(a.n_out, kB)), dim3(kB), 0, s, a);
@@ -1662,7 +1366,7 @@ void launch_obs_finish(const ObsFinishArgs& a, hipStream_t s) {
   else
     hipLaunchKernelGGL(k_obs_finish, dim3(nblk(a.n_out, kB / 64)), dim3(kB), 0, s, a);
 }
-void launch_normalise(const NormArgs& a, hipStream_t s) {
+static void launch_normalise(const NormArgs& a, hipStream_t s) {
   const dim3 g(nblk(a.P, kB), (unsigned)a.F);
   const unsigned nbm = nblk(a.P, kB) < kMaxNormBlocks ? nblk(a.P, kB) : kMaxNormBlocks;
   if (!a.bmax) hipLaunchKernelGGL(k_norm_max, dim3(nbm, (unsigned)a.F), dim3(kB), 0, s, a);
@@ -1681,10 +1385,9 @@ void launch_resample(const ResampleArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_readout, dim3((unsigned)a.F), dim3(1024), 0, s, a);
 }
 // normalise + resample + read-out: one launch for small filters (k_small_resample, bitwise
-// the multi-kernel path), the multi-kernel path otherwise (GPMDM_NO_SMALL_PATH=1 forces it)
+// the multi-kernel path), the multi-kernel path otherwise
 bool small_resample_ok(const NormArgs& na, const ResampleArgs& ra) {
-  static const bool no_small = std::getenv("GPMDM_NO_SMALL_PATH") != nullptr;
-  return !no_small && na.P <= kSmallP && ra.GB == 0;
+  return small_path_enabled() && na.P <= kSmallP && ra.GB == 0;
 }
 
 void launch_normalise_resample(const NormArgs& na, const ResampleArgs& ra, hipStream_t s) {

@@ -60,7 +60,7 @@ constexpr int kChunk = 1024;                   // H entries per chunk (4 per thr
 constexpr int kMaxChunks = 4096;               // k_ubucket_scatter scans the chunk totals in LDS
 __global__ __launch_bounds__(kT) void k_ubucket_chunk_scan(int* H, long long n, int* chunk_tot) {
   __shared__ int wtot[kT / 64];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const long long base = (long long)blockIdx.x * kChunk + tid * 4;
   int v[4], t = 0;
 #pragma unroll
@@ -68,16 +68,7 @@ __global__ __launch_bounds__(kT) void k_ubucket_chunk_scan(int* H, long long n, 
     v[k] = base + k < n ? H[base + k] : 0;
     t += v[k];
   }
-  int x = t;                                   // inclusive wave scan of the thread totals
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(x, off);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) wtot[w] = x;
-  __syncthreads();
-  int run = x - t;
-  for (int u = 0; u < w; ++u) run += wtot[u];
+  int run = block_inclusive_scan(t, 0, OpSum(), wtot, threadIdx.x >> 6) - t;   // the thread totals before this one
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     if (base + k < n) H[base + k] = run;
@@ -95,7 +86,7 @@ __global__ __launch_bounds__(kT) void k_ubucket_scatter(long long P, unsigned fr
   __shared__ int run[kT];                      // the block's earlier rounds' counts per bucket
   __shared__ int coff[kMaxChunks];             // exclusive prefix of the chunk totals
   __shared__ int wtot[kW];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x, w = tid >> 6;
   {                                            // every block scans the (few) chunk totals itself
     int v[kCPer], t = 0;
 #pragma unroll
@@ -104,16 +95,7 @@ __global__ __launch_bounds__(kT) void k_ubucket_scatter(long long P, unsigned fr
       v[k] = c < nchunk ? chunk_tot[c] : 0;
       t += v[k];
     }
-    int x = t;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int y = __shfl_up(x, off);
-      if (lane >= off) x += y;
-    }
-    if (lane == 63) wtot[w] = x;
-    __syncthreads();
-    int e = x - t;
-    for (int u = 0; u < w; ++u) e += wtot[u];
+    int e = block_inclusive_scan(t, 0, OpSum(), wtot, w) - t;
 #pragma unroll
     for (int k = 0; k < kCPer; ++k) {
       coff[tid * kCPer + k] = e;
@@ -135,7 +117,7 @@ __global__ __launch_bounds__(kT) void k_ubucket_scatter(long long P, unsigned fr
     }
     const unsigned long long valid = __ballot(b >= 0);
     same &= b >= 0 ? valid : ~valid;
-    const int r_wave = __popcll(same & ((1ull << lane) - 1));
+    const int r_wave = mask_rank(same);
     __syncthreads();
     if (b >= 0 && r_wave == 0) cnt[w][b] = __popcll(same);   // one writer per (wave, bucket)
     __syncthreads();
