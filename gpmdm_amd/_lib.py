@@ -63,6 +63,15 @@ class SmoothedOut(ctypes.Structure):
                 ("obs_spread", _dp), ("ancestors", _i64p), ("states", _dp), ("classes", _i64p)]
 
 
+class MarginalOut(ctypes.Structure):
+    """gpmdm_marginal_out: host arrays, any may be NULL."""
+    _fields_ = [("class_prob", _dp), ("state_mean", _dp), ("mass", _dp), ("ess", _dp), ("ess_distinct", _dp),
+                ("weights", _dp)]
+
+
+GPMDM_BACKSMOOTH_MAX_PAIRS = 1 << 36
+
+
 class InnovationOut(ctypes.Structure):
     """gpmdm_innovation_out: host arrays, any may be NULL."""
     _fields_ = [("mean", _dp), ("spread", _dp), ("gp_variance", _dp), ("variance", _dp), ("residual", _dp),
@@ -135,6 +144,9 @@ _SIGS = {
     "gpmdm_bank_forecast": (c_int, [c_void_p, c_int, c_int, POINTER(c_uint64), POINTER(ForecastOut), c_void_p]),
     "gpmdm_bank_set_smoothing": (c_int, [c_void_p, c_int]),
     "gpmdm_bank_smoothed": (c_int, [c_void_p, c_int, c_int, POINTER(SmoothedOut), c_void_p]),
+    "gpmdm_backward_step": (c_int, [c_void_p, _dp, c_int64, _dp, _i64p, _dp, c_int64, _dp, _i64p, _dp, _dp, _dp,
+                                    c_void_p]),
+    "gpmdm_pf_smoothed_marginal": (c_int, [c_void_p, c_int, c_int, POINTER(MarginalOut), c_void_p]),
     "gpmdm_pf_set_predictive": (c_int, [c_void_p, c_int]),
     "gpmdm_pf_innovation": (c_int, [c_void_p, POINTER(InnovationOut), c_void_p]),
     "gpmdm_pf_observation_gp": (c_int, [c_void_p, _dp, c_void_p]),

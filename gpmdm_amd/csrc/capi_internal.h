@@ -18,6 +18,8 @@
 //   capi_forecast.hip  the multi-step forecast roll-out (gpmdm_pf_forecast, gpmdm_bank_forecast)
 //   capi_smooth.hip    fixed-lag smoothing: the ancestry ring and its read-out (gpmdm_pf_smoothed,
 //                      gpmdm_bank_smoothed)
+//   capi_backsmooth.hip  marginal backward smoothing over that ring (gpmdm_backward_step,
+//                      gpmdm_pf_smoothed_marginal)
 //   capi_innov.hip     per-joint innovations and the GP's predictive variance (gpmdm_pf_set_predictive,
 //                      gpmdm_pf_innovation, gpmdm_pf_observation_gp and the banks')
 //   capi_gate.hip      outlier gating inside the frame (gpmdm_pf_set_gate, gpmdm_pf_gate_report)
@@ -133,6 +135,14 @@ struct GpImage {
 
 int build_image(GpImage& g, int n_rows, int d, int n_m, const double* X, const double* ls,
                 const double* lin_c2, const double* R, const double* M, TileGeo geo);
+
+// One backward step's device scratch (capi_backsmooth.hip bs_step): the sources' records, one
+// class's dynamics moments and tile partials, the targets' grouping, the ranges' partial sums,
+// the targets' exponents, and the multiplicity histogram of a slot
+struct BsScratch {
+  DevBuf<double> rec, mu, var, q, part, lw;
+  DevBuf<int> perm, tab, hist, mult;
+};
 
 }  // namespace gpmdm::capi
 
@@ -392,6 +402,14 @@ struct gpmdm_pf {
   Landing sm_out;
   DevBuf<unsigned char> sm_marks;
   int sm_slot() const { return (int)(frame % (unsigned)(sm_L + 1)); }   // the latest frame's
+  // Marginal backward smoothing over the same ring (gpmdm_pf_smoothed_marginal, backsmooth.h;
+  // capi_backsmooth.hip): scratch of its own, grown on demand, and the result rows with their
+  // pinned landing buffer (sm_wait covers bs_out).  sm_root_anc: the oldest slot in reach (lag
+  // sm_depth) was recorded by a resample, so its ancestors are real (a cleared ring's root has none).
+  bool sm_root_anc = false;
+  BsScratch bs;
+  DevBuf<double> bs_w[2], bs_stage;
+  Landing bs_out;
   // Innovations and the GP's predictive variance (gpmdm_pf_set_predictive, gpmdm_pf_innovation,
   // gpmdm_pf_observation_gp and the banks'; obs_innov.h, capi_innov.hip).  predictive: every
   // weigh keeps vc = 1 - k^T K_y^-1 k of its particles in vc_prop (F x Pf, the order of X_prop
@@ -755,6 +773,11 @@ void launch_dyn_tiles(const gpmdm_model* m, const std::vector<GpImage>& dset, Ti
                       const int* perm, const double* X, long long rows_ub, double* q, long long ld_q, double* mu,
                       hipStream_t s);
 int sm_set(gpmdm_pf* pf, int lag);     // (set_smoothing of a checked handle, single or bank)
+// gpmdm_predict_dyn's launches for class c over n device rows, q: predict_dyn_scratch doubles
+// (capi_model.hip)
+size_t predict_dyn_scratch(const gpmdm_model* m, int c, long long n);
+void launch_predict_dyn(const gpmdm_model* m, int c, const double* Xs, long long n, double* mu, double* var,
+                        double* q, hipStream_t s);
 int iv_wait(gpmdm_pf* pf);             // an innovation call's launches in flight (capi_innov.hip)
 // gating (capi_gate.hip): the end of a gated-mode weigh on s; the log il2 table of the filter's
 // (new) model

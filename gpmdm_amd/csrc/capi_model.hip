@@ -157,6 +157,52 @@ static int finish_scratch(double* q, hipStream_t s) {
   return GPMDM_OK;
 }
 
+// gpmdm_predict_dyn's launches (segment table, dynamics tiles, finish) for class c over the n
+// device rows Xs, with scratch q of predict_dyn_scratch doubles: one builder for the entry point
+// and the backward smoother's moments (capi_backsmooth.hip), so both give the same bits.
+size_t predict_dyn_scratch(const gpmdm_model* m, int c, long long n) {
+  return (size_t)m->dyn_set(n >= kWideRows)[c].n_parts() * (size_t)n + 4;
+}
+
+void launch_predict_dyn(const gpmdm_model* m, int c, const double* Xs, long long n, double* mu, double* var,
+                        double* q, hipStream_t s) {
+  const GpImage& g = m->dyn_set(n >= kWideRows)[c];
+  const int nparts = g.n_parts();
+  TileParams tp{};
+  tp.seg[0] = g.seg();
+  tp.n_seg = 1;
+  tp.geo = g.geo;
+  tp.tiles_ub = g.tiles(n);
+  tp.n_j_max = g.n_j;
+  int* tab = reinterpret_cast<int*>(q + (size_t)nparts * n);   // segment table after q
+  launch_seg_table(tab, (int)n, g.tiles(n), s);
+  tp.seg_pos_begin = tab + 0;
+  tp.seg_pos_end = tab + 1;
+  tp.seg_out_base = tab + 2;
+  tp.seg_tile_start = tab + 3;
+  tp.X = Xs;
+  fill_tile_common(tp, m, true);
+  tp.qpart = q;
+  tp.ld_q = n;
+  tp.mu = mu;
+  tp.ld_mu = m->d;
+  launch_gp_tile(tp, m->d, true, s);
+  DynFinishArgs fa{};
+  fa.n_out = n;
+  fa.n_seg = 1;
+  fa.d = m->d;
+  fa.n_parts[0] = nparts;
+  fa.qpart = q;
+  fa.ld_q = n;
+  fa.mu = mu;
+  fa.ld_mu = m->d;
+  fa.X = Xs;
+  for (int j = 0; j <= m->d; ++j) fa.lin_c2[j] = m->x_lin_c2[j];
+  for (int j = 0; j < m->d; ++j) fa.il2[j] = m->x_il2[j];
+  fa.var_out = var;
+  launch_dyn_finish(fa, s);
+}
+
 }  // namespace gpmdm::capi
 
 extern "C" {
@@ -376,43 +422,9 @@ int gpmdm_predict_dyn(gpmdm_model_t m, int c, const double* Xs, int64_t n, doubl
   CHECK(Xs && mu && var, "null buffer");
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipSetDevice(m->device));
-  const GpImage& g = m->dyn_set(n >= kWideRows)[c];
-  const int nparts = g.n_parts();
   double* q = nullptr;                 // per-call scratch, stream-ordered (see gpmdm_predict_obs)
-  HIPCHK(hipMallocAsync((void**)&q, sizeof(double) * ((size_t)nparts * n + 4), s));
-  TileParams tp{};
-  tp.seg[0] = g.seg();
-  tp.n_seg = 1;
-  tp.geo = g.geo;
-  tp.tiles_ub = g.tiles(n);
-  tp.n_j_max = g.n_j;
-  int* tab = reinterpret_cast<int*>(q + (size_t)nparts * n);   // segment table after q
-  launch_seg_table(tab, (int)n, g.tiles(n), s);
-  tp.seg_pos_begin = tab + 0;
-  tp.seg_pos_end = tab + 1;
-  tp.seg_out_base = tab + 2;
-  tp.seg_tile_start = tab + 3;
-  tp.X = Xs;
-  fill_tile_common(tp, m, true);
-  tp.qpart = q;
-  tp.ld_q = n;
-  tp.mu = mu;
-  tp.ld_mu = m->d;
-  launch_gp_tile(tp, m->d, true, s);
-  DynFinishArgs fa{};
-  fa.n_out = n;
-  fa.n_seg = 1;
-  fa.d = m->d;
-  fa.n_parts[0] = nparts;
-  fa.qpart = q;
-  fa.ld_q = n;
-  fa.mu = mu;
-  fa.ld_mu = m->d;
-  fa.X = Xs;
-  for (int j = 0; j <= m->d; ++j) fa.lin_c2[j] = m->x_lin_c2[j];
-  for (int j = 0; j < m->d; ++j) fa.il2[j] = m->x_il2[j];
-  fa.var_out = var;
-  launch_dyn_finish(fa, s);
+  HIPCHK(hipMallocAsync((void**)&q, sizeof(double) * predict_dyn_scratch(m, c, n), s));
+  launch_predict_dyn(m, c, Xs, n, mu, var, q, s);
   TRY(finish_scratch(q, s));
   HIPCHK(m->note_use(s));   // the model's release is ordered after this map (lifecycle waits)
   return GPMDM_OK;

@@ -19,6 +19,7 @@ int sm_wait(gpmdm_pf* pf) {
     HIPCHK(pf->sm_ev.sync());
     pf->sm_pending = false;
   }
+  TRY(pf->bs_out.wait());
   return pf->sm_out.wait();
 }
 
@@ -41,6 +42,7 @@ int sm_record(gpmdm_pf* pf, hipStream_t s) {
   launch_record(pf, s);
   HIPCHK(hipGetLastError());
   // (a frame counter that wrapped starts a new history: slots follow the counter)
+  if (pf->frame == 0 || pf->sm_depth == pf->sm_L) pf->sm_root_anc = true;   // the oldest slot in reach is a resample's
   pf->sm_depth = pf->frame == 0 ? 0 : std::min(pf->sm_L, pf->sm_depth + 1);
   HIPCHK(pf->sm_ev.record(s));
   pf->sm_pending = true;
@@ -53,6 +55,7 @@ int sm_record(gpmdm_pf* pf, hipStream_t s) {
 // lifecycle stream, synchronised here.
 int sm_clear(gpmdm_pf* pf, hipStream_t s) {
   pf->sm_depth = 0;
+  pf->sm_root_anc = false;
   if (pf->sm_L == 0 || !pf->initialised) return GPMDM_OK;
   launch_record(pf, s);
   HIPCHK(hipGetLastError());

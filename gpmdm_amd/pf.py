@@ -111,6 +111,64 @@ class Smoothed:
     classes: Optional[torch.Tensor] = None              # (n, P) int64
 
 
+@dataclass
+class MarginalSmoothed:
+    """``GPMDM_PF.smoothed_marginal``'s result; row i is lag ``lags[i]``, i.e. frame ``frames[i]``.
+    ``ess`` counts copies of a resampled particle as support and is flattered by them;
+    ``ess_distinct`` is the effective number of distinct support points, to be read beside
+    ``Smoothed.distinct_ancestors``."""
+    lags: torch.Tensor                                  # (n,) int64
+    frames: torch.Tensor                                # (n,) int64: frame - lag
+    class_probabilities: torch.Tensor                   # (n, C)
+    state_mean: torch.Tensor                            # (n, d)
+    mass: torch.Tensor                                  # (n,)  1 to rounding; never renormalised
+    ess: torch.Tensor                                   # (n,)
+    ess_distinct: torch.Tensor                          # (n,)
+    weights: Optional[torch.Tensor] = None              # (n, P): of frame - lag's recorded cloud
+
+
+def backward_step(model, T, Xs, cs, Xt, ct, wt, a=None):
+    """One step of the marginal backward smoother (gpmdm_backward_step): sources ``Xs`` (n_s, d),
+    ``cs`` with filter weights ``a`` (None: 1 / n_s each), targets ``Xt`` (n_t, d), ``ct`` with
+    smoothing weights ``wt``, transition density f = T[c, c'] N(x'; mu_c'(x), v_c'(x)) with the
+    moments of ``model.map_x_dynamics_for_class``.  Returns ``(weights, log_den)`` as CPU tensors:
+    ``weights[i] = a_i sum_j wt_j f_ij / D_j`` and ``log_den[j] = log D_j``, ``D_j = sum_k a_k f_kj``
+    (-inf, and the target's mass lost, when no source reaches j).  A pure, bit-reproducible
+    function of its inputs."""
+    d, C = int(model.d), int(model.n_classes)
+
+    def arr(x, shape, what, dtype=np.float64):
+        if isinstance(x, torch.Tensor):
+            x = x.detach().cpu().numpy()
+        x = np.asarray(x)
+        if dtype is np.int64 and x.dtype.kind not in "iu":
+            raise ValueError(f"{what} must hold integers, got dtype {x.dtype}")
+        x = np.ascontiguousarray(x, dtype=dtype)
+        if x.ndim != len(shape) or any(s is not None and s != n for s, n in zip(shape, x.shape)):
+            raise ValueError(f"{what} must have shape {tuple('n' if s is None else s for s in shape)}, got {x.shape}")
+        return x
+
+    Tm = arr(T, (C, C), "T")
+    Xs_, Xt_ = arr(Xs, (None, d), "Xs"), arr(Xt, (None, d), "Xt")
+    n_s, n_t = Xs_.shape[0], Xt_.shape[0]
+    if n_s < 1 or n_t < 1:
+        raise ValueError("backward_step needs at least one source and one target")
+    cs_, ct_ = arr(cs, (n_s,), "cs", np.int64), arr(ct, (n_t,), "ct", np.int64)
+    wt_ = arr(wt, (n_t,), "wt")
+    a_ = None if a is None else arr(a, (n_s,), "a")
+    for what, c in (("cs", cs_), ("ct", ct_)):
+        if c.min() < 0 or c.max() >= C:
+            raise ValueError(f"{what} must lie in [0, {C})")
+    if n_s * n_t > _lib.GPMDM_BACKSMOOTH_MAX_PAIRS:
+        raise ValueError(f"backward_step serves up to 2^36 source-target pairs, got {n_s} x {n_t}")
+    ws, ld = np.zeros(n_s), np.zeros(n_t)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(model.device).cuda_stream)
+    _lib.check(_lib.load().gpmdm_backward_step(model.handle, _lib.dptr(Tm), n_s, _lib.dptr(Xs_), _lib.i64ptr(cs_),
+                                               _lib.dptr(a_), n_t, _lib.dptr(Xt_), _lib.i64ptr(ct_), _lib.dptr(wt_),
+                                               _lib.dptr(ws), _lib.dptr(ld), stream), "backward_step")
+    return torch.from_numpy(ws), torch.from_numpy(ld)
+
+
 class Innovation(NamedTuple):
     """``GPMDM_PF.innovation``'s result (CPU tensors; a bank's carry a leading filter axis): how
     surprising each joint of the frame just weighed was, against the propagated (pre-resample,
@@ -904,6 +962,46 @@ class GPMDM_PF:
         lags, rest = _smoothed_call(self, "filter", "gpmdm_pf_smoothed", (), lag, observation, particles)
         t = lambda a: None if a is None else torch.from_numpy(a)   # noqa: E731
         return Smoothed(t(lags), t(self.frame - lags), *map(t, rest))
+
+    def smoothed_marginal(self, lag=None, *, particles: bool = False) -> MarginalSmoothed:
+        """What was happening ``lag`` frames ago, given what has been seen since, as a distribution
+        over that frame's whole recorded cloud: the forward-filter backward marginal smoother
+        (gpmdm_pf_smoothed_marginal).  With w_0 = 1/P on the current cloud, each lag's weights come
+        from the previous lag's by one ``backward_step`` against the filter's own proposal (class
+        switch, then the new class's dynamics GP); row l holds sum_i w_l,i [c_i = c], sum_i w_l,i X_i,
+        the mass sum_i w_l,i (1 to rounding, never renormalised), ``ess`` = mass^2 / sum w^2,
+        ``ess_distinct`` = mass^2 / sum m_i w_i^2 with m_i the copies of particle i's resampling
+        ancestor in its frame, and with ``particles`` the weights themselves.  ``lag`` as in
+        ``smoothed``.  ``ess`` counts copies as support; read ``ess_distinct`` beside
+        ``smoothed().distinct_ancestors``.
+
+        Prefer ``smoothed`` for whole trajectories, poses and near lags (its cost is O(P) per lag);
+        prefer this one wherever ``distinct_ancestors`` has collapsed (its cost is O(P^2) per lag).
+        No draw, no state change: later updates are bitwise those without the call, and the same
+        history gives the same bits.  Single filters on one rank, up to 262144 particles."""
+        first, last = _check_lag_range(lag)
+        if self._peers or getattr(self, "_world", 1) > 1:
+            raise ValueError("smoothed_marginal serves filters on one rank, not sharded filters")
+        P = self._num_particles
+        if P * P > _lib.GPMDM_BACKSMOOTH_MAX_PAIRS:
+            raise ValueError(f"smoothed_marginal serves up to 262144 particles (2^36 pairs per step), got {P}")
+        if not self._smoothing_lag:
+            raise ValueError("smoothing is off: build the filter with smoothing_lag=L or call set_smoothing(L)")
+        depth = self.smoothing_depth
+        if last is None:
+            last = depth
+        if last > depth:
+            raise ValueError(f"lag {last} is above the recorded depth {depth} (smoothing lag {self._smoothing_lag})")
+        C, d, n = self.num_classes, self.latent_dim, last - first + 1
+        cp, sm = np.zeros((n, C)), np.zeros((n, d))
+        ms, es, ed = np.zeros(n), np.zeros(n), np.zeros(n)
+        w = np.zeros((n, P)) if particles else None
+        out = _lib.MarginalOut(*map(_lib.dptr, (cp, sm, ms, es, ed, w)))
+        _lib.check(_lib.load().gpmdm_pf_smoothed_marginal(self._h, first, last, ctypes.byref(out), self._stream()),
+                   "smoothed_marginal")
+        lags = np.arange(first, last + 1, dtype=np.int64)
+        t = lambda x: None if x is None else torch.from_numpy(x)   # noqa: E731
+        return MarginalSmoothed(t(lags), t(self.frame - lags), *map(t, (cp, sm, ms, es, ed, w)))
 
     @property
     def frame(self) -> int:

@@ -764,6 +764,58 @@ int gpmdm_rng_walk_states(gpmdm_rng_walk_t walk, int64_t n, const int64_t* draws
                           uint8_t* out_states);
 int gpmdm_rng_walk_destroy(gpmdm_rng_walk_t walk);
 
+/* Marginal backward smoothing over the history ring: the forward-filter backward marginal
+ * smoother (FFBSm).  Where gpmdm_pf_smoothed follows the few ancestors that survived every
+ * resample since, this re-weights each past frame's whole cloud by what was seen since; it
+ * takes no draw and keeps no second ring.  The transition density is the filter's proposal
+ * (gpmdm_pf.py:137-168): the class switches, then the state moves under the new class's dynamics
+ * GP.  For a source (x, c) and a target (x', c'),
+ *   log f = log T[c, c'] - 1/2 sum_q [(x'_q - mu_q)^2 / v_q + log v_q] - (d/2) log 2 pi,
+ * mu, v = gpmdm_predict_dyn(model, c', x)'s mean and variance -- the same launches on the source
+ * rows in their given order, so the same bits.  log 0 = -inf gives f = 0, and a source whose v is
+ * non-positive or non-finite for class c' has f = 0 towards class-c' targets.
+ * gpmdm_backward_step (host arrays; a pure function of its inputs): sources Xs (n_s x d), cs with
+ * filter weights a (NULL: 1 / n_s each), targets Xt (n_t x d), ct with smoothing weights wt;
+ *   D_j = sum_k a_k f_kj,            log_den_out[j] = log D_j (-inf when no source reaches j),
+ *   ws_out[i] = a_i sum_j wt_j f_ij / D_j   (targets with D_j = 0 contribute 0: their mass is lost).
+ * Everything is summed on logarithms (a running power-of-two scale, rescaled exactly), in an order
+ * that is a function of (n_s, n_t, C) alone and without floating-point atomics: the same inputs
+ * give the same bits, and two sources with bitwise-equal (x, c, a) get bitwise-equal weights.
+ * GPMDM_E_INVALID: a class outside [0, C), more than 2^36 pairs, or more than 1 GiB of staging
+ * for the sources' moments (C x n_s x (2 d + 1) doubles).  ws_out and log_den_out may be NULL.
+ * gpmdm_pf_smoothed_marginal: with t the last completed frame, w_0 = 1/P on its cloud, and for
+ * l = 0 .. lag_last - 1 one backward step with targets = frame t - l's recorded cloud carrying w_l
+ * and sources = frame t - l - 1's with equal weights.  Row l - lag_first of each output that is not
+ * NULL holds
+ *   class_prob[c] = sum_i w_l,i [c_i = c],   state_mean = sum_i w_l,i X_i,
+ *   mass          = sum_i w_l,i   (1 to rounding on a real history; never renormalised),
+ *   ess           = mass^2 / sum_i w_l,i^2           (counts copies, and is flattered by them),
+ *   ess_distinct  = mass^2 / sum_i m_i w_l,i^2, m_i = the particles of the slot that share i's
+ *                   resampling ancestor (an integer histogram; 1 for a cleared ring's root):
+ *                   copies carry equal weights, so this is the effective number of distinct
+ *                   support points -- the number to read beside gpmdm_pf_smoothed's `distinct`,
+ *   weights       = w_l per particle of frame t - l, in the ring's (gpmdm_pf_export's) order.
+ * Every sum has a fixed order.  The rules are gpmdm_pf_smoothed's: 0 <= lag_first <= lag_last <=
+ * depth, GPMDM_E_INVALID otherwise or with smoothing off, GPMDM_E_STATE between a switch and its
+ * resample; the live filter is untouched (no draw, no frame or health counter, a pending
+ * pre-switch stays pending, later frames are bitwise those without the call); everything is
+ * queued on `stream` and ends with one copy-out and one wait; the scratch is the call's own,
+ * grown on demand.  GPMDM_E_INVALID, decided before any launch: banks, sharded filters
+ * (n_ranks > 1), more than 2^36 pairs per step (P > 262144), more than 1 GiB of staging. */
+typedef struct gpmdm_marginal_out {   /* host arrays; any may be NULL; n = lag_last - lag_first + 1 */
+  double* class_prob;     /* n x C */
+  double* state_mean;     /* n x d */
+  double* mass;           /* n */
+  double* ess;            /* n */
+  double* ess_distinct;   /* n */
+  double* weights;        /* n x P */
+} gpmdm_marginal_out;
+int gpmdm_backward_step(gpmdm_model_t model, const double* T, int64_t n_s, const double* Xs, const int64_t* cs,
+                        const double* a, int64_t n_t, const double* Xt, const int64_t* ct, const double* wt,
+                        double* ws_out, double* log_den_out, void* stream);
+int gpmdm_pf_smoothed_marginal(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_marginal_out* out,
+                               void* stream);
+
 /* Message of the last failed call on this thread ("" if none). */
 const char* gpmdm_last_error(void);
 
