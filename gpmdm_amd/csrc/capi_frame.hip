@@ -508,6 +508,8 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
       tp.perm = obs_order;
       tp.X = pf->X_prop;
       fill_tile_common(tp, m, false);
+      tp.t_flush = m->t_flush;          // the likelihood flushes at the model's tau (the maps do not)
+      tp.skip = pf->obs_skip ? 1 : 0;
       tp.qpart = pf->qobs;
       tp.ld_q = nl;
       tp.spart = pf->sobs;

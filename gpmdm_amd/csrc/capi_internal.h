@@ -194,6 +194,11 @@ struct gpmdm_model {
   bool has_cutoff() const { return obs_cut.Bt != nullptr; }
   double cut_tau = 0.0, cut2 = 0.0, t_cut = 0.0;
   void release_cutoff() { obs_cut = CutImage{}; }
+  // The dense filter's flush (gpmdm_model_set_obs_flush): tau from the column sums of K_y^-1 Y
+  // kept at creation, and t_flush = ln tau in the generation's exponent units (as t_cut; negative);
+  // 0: nothing is flushed
+  std::vector<double> obs_m1;
+  double flush_tau = 0.0, t_flush = 0.0;
 
   // Lifecycle (DESIGN.md §1 "Lifecycle waits"): the filters built on the model --
   // gpmdm_model_set_obs_cutoff waits for each one's own last frame (quiesce) before it
@@ -287,6 +292,9 @@ struct gpmdm_pf {
   // the observation GP's kernel-value cutoff (gpmdm_pf_set_obs_cutoff): on, and the skip
   // statistics of the cutoff kernel (device: MFMA groups run, the dense kernel's count)
   bool obs_cutoff = false;
+  // the dense tile branches around all-zero 16 x 4 blocks of kernel values (gpmdm_pf_set_obs_skip;
+  // off: the same kernel runs every block)
+  bool obs_skip = true;
   DevBuf<unsigned long long> sp_stats;
   bool sp_stats_on = false;
   // AUTO (gpmdm_pf_set_obs_cutoff mode 3; single-rank filters and banks with mapped

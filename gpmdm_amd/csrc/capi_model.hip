@@ -145,6 +145,9 @@ const GpImage& obs_pick(const gpmdm_model* m, long long P, long long n, TileGeo&
 void fill_tile_common(TileParams& tp, const gpmdm_model* m, bool dyn) {
   const int d = m->d;
   for (int j = 0; j < d; ++j) tp.ls[j] = dyn ? m->x_ls[j] : m->y_ls[j];
+  // no flush (the filter's weigh alone sets one, capi_frame.hip); exact-zero blocks are skipped
+  tp.t_flush = 0.0;
+  tp.skip = 1;
 }
 
 // The predictive maps' per-call scratch is released in stream order on every exit after
@@ -233,6 +236,7 @@ int gpmdm_model_create(const gpmdm_model_desc* desc, int device, gpmdm_model_t* 
   m->x_ls.assign(desc->x_lengthscales, desc->x_lengthscales + d);
   m->x_lin_c2.assign(desc->x_lin_coeff2, desc->x_lin_coeff2 + d + 1);
   m->x_il2.assign(desc->x_inv_lambda2, desc->x_inv_lambda2 + d);
+  m->obs_m1 = column_l1(m->N, desc->obs_beta, m->D);      // (gpmdm_model_set_obs_flush)
   // tile shapes: the observation GP defaults to 32x512 (half the kernel-value generation per
   // MFMA of 64x256, tools/microbench/tile_bench.hip); the dynamics GPs use 64-particle tiles
   // (their class-grouped tile starts are computed on the device in 64s, pf_kernels.hip)
@@ -358,6 +362,24 @@ int gpmdm_model_obs_cutoff_image(gpmdm_model_t m, int64_t* n, double* out) {
 int gpmdm_model_obs_cutoff(gpmdm_model_t m, double* tau) {
   CHECK(m && tau, "null argument");
   *tau = m->has_cutoff() ? m->cut_tau : 0.0;
+  return GPMDM_OK;
+}
+
+// The dense filter's flush: the cutoff's tau (host_image.h obs_cutoff_tau) from the column sums
+// of K_y^-1 Y kept at creation.  The filters read t_flush when they launch a frame's weigh.
+int gpmdm_model_set_obs_flush(gpmdm_model_t m, double sigma2, const double* y_absmax) {
+  CHECK(m && y_absmax, "null argument");
+  CHECK(sigma2 > 0.0 && std::isfinite(sigma2), "sigma2 must be positive (the observation noise variance)");
+  const double tau = obs_cutoff_tau_l1(m->N, sigma2, m->obs_m1.data(), m->D, y_absmax);
+  CHECK(tau > 0.0 && tau < 1.0 && std::isfinite(tau), "no usable flush threshold for this model");
+  m->flush_tau = tau;
+  m->t_flush = std::log(tau) * kLog2eX64;
+  return GPMDM_OK;
+}
+
+int gpmdm_model_obs_flush(gpmdm_model_t m, double* tau) {
+  CHECK(m && tau, "null argument");
+  *tau = m->flush_tau;
   return GPMDM_OK;
 }
 

@@ -724,6 +724,13 @@ int gpmdm_bank_observation(gpmdm_pf_t pf, double* mean, double* spread, void* st
   return GPMDM_OK;
 }
 
+int gpmdm_pf_set_obs_skip(gpmdm_pf_t pf, int on) {
+  CHECK(pf, "null handle");
+  if (pf->dyn_done || pf->propagated) return fail(GPMDM_E_STATE, "set_obs_skip between propagate and resample");
+  pf->obs_skip = on != 0;
+  return GPMDM_OK;
+}
+
 int gpmdm_pf_obs_cutoff_auto(gpmdm_pf_t pf, int* last_cut, double* fraction) {
   CHECK(pf, "null handle");
   HIPCHK(pf->cut_auto_collect());

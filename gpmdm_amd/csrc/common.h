@@ -47,6 +47,12 @@ struct TileParams {
   // a masked bank (gpmdm_bank_set_obs_masks): lam2 is F x n_m, row pos / Pf as z; 0: one row
   // for every filter (single filters, unmasked banks)
   long long lam_ld;
+  // Flush and skip (gp_tile.h): generated values whose exponent (in the generation's units,
+  // 64 x / ln 2) is below t_flush < 0 become exactly 0 (0: no flush); skip != 0 branches around
+  // the MFMAs of all-zero 16-particle x 4-row blocks of K*, 0 runs them.  (A zeroed TileParams:
+  // neither.)
+  double t_flush;
+  int skip;
 };
 
 void launch_gp_tile(const TileParams& p, int d, bool dyn, hipStream_t stream);

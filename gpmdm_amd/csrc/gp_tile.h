@@ -94,8 +94,16 @@ __device__ __forceinline__ double exp2_64(double t, const double* tab) {
 // kTileLamRows -- the fused likelihood epilogue reads lam2 as F rows (TileParams::lam_ld), the
 // row of each particle's filter: the instantiations only a masked bank launches, so every
 // other launch runs the epilogue with one row, unchanged.
+// kTileNoSkip -- the K loop runs every MFMA (no activity words, no branch): the shapes whose
+// register budget cannot take the branch without spilling (kNoSkip32x512).  The flush is the same
+// either way, so the values are too.
 constexpr int kTileCoordLDS = 131072;
 constexpr int kTileLamRows = 262144;
+constexpr int kTileNoSkip = 524288;
+// 32 x 512 at d = 11, 12 runs at the 256-VGPR limit of two workgroups per CU: with the branch
+// it spills 14 - 16 VGPRs into the K loop (tools/tile_resources.py), so it runs without it.
+template <int DI>
+constexpr int kNoSkip32x512 = (DI == 11 || DI == 12) ? kTileNoSkip : 0;
 template <int I, int E, class F>
 __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (I < E) {
@@ -108,7 +116,8 @@ template <int DI, bool DYN, int FLAGS = 0, int NW = 4, int MT = 4, int NTW = 4>
 __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const TileParams prm) {
   static_assert(MT == 1 || MT == 2 || MT == 4, "MT");
   static_assert(NTW == 4 || NTW == 6 || NTW == 8 || NTW == 16, "NTW");
-  static_assert((FLAGS & ~(kTileCoordLDS | kTileLamRows)) == 0, "FLAGS");
+  static_assert((FLAGS & ~(kTileCoordLDS | kTileLamRows | kTileNoSkip)) == 0, "FLAGS");
+  constexpr bool SKIP = (FLAGS & kTileNoSkip) == 0;
   static_assert(!DYN || !(FLAGS & kTileLamRows), "lam2 rows: the observation GP's epilogue");
   constexpr bool LROWS = (FLAGS & kTileLamRows) != 0;
   // B fragments in flight: BR sub-steps (a full K-step, 4, for NTW <= 8; 2 for NTW = 16,
@@ -142,6 +151,13 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
   constexpr int RA = 2 * SB;                                 // row staging lookahead
   __shared__ double As[ASL][kBK][LDA];
   __shared__ double RX[RXS][RPT * NT];                        // row records, then padding
+  // Activity words, one per wave per K* slot (the slots' discipline is As's): bit kk MT + mt of
+  // wave w's word says that among the values w generated for that K-step, the 16 particles of row
+  // block mt have a non-zero one among training rows 4 kk .. 4 kk + 3.  The OR of a slot's NW
+  // words covers the whole K* tile; a clear bit's A fragment is exactly zero, so its MFMAs add
+  // nothing (acc + 0 b = acc for finite b) and the K loop branches around them.  Flushed
+  // (TileParams::t_flush), underflowed and padding values all clear their bits by being 0.
+  __shared__ unsigned Mk[ASL][NW];
   constexpr double kScale = kLog2eX64;
   // exp table 2^(j/64), one shared copy (lanes reading entries j and j + 32 in one lane
   // group conflict; a lane-replicated table removes the conflicts and costs more in
@@ -281,13 +297,31 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
   // |Xs|^2 = kPadSq (2^28, geometry.h), so a padding row's exponent is about -2^28 x 64/ln2
   // (the float->int conversion is exact, ldexp underflows): its kernel value is exactly 0,
   // no masking per value.
+  const double t_flush = prm.t_flush < 0.0 ? prm.t_flush : -__builtin_inf();   // (0: no flush)
   auto gen_one = [&](int rb, int s) -> double {
     const int r = g + NG * s;
     const double* row = &RX[rb][r * RW];
     double x = -(asq + row[DI]);
 #pragma unroll
     for (int j = 0; j < DI; ++j) x = fma(PLDS ? PA[m][j] : a2[j], row[j], x);
-    return exp2_64(x, tab);                                // padding rows: exactly 0
+    const double e = exp2_64(x, tab);                      // padding rows: exactly 0
+    return x < t_flush ? 0.0 : e;                          // the flush: below tau, exactly 0
+  };
+  // this wave's activity word for the values it generated (lanes 16 q .. 16 q + 15 share a row
+  // block and a training row: wave-uniform arithmetic on the compare's lane mask)
+  auto mask_word = [&](const double (&v)[GV]) -> unsigned {
+    unsigned wd = 0;
+#pragma unroll
+    for (int s = 0; s < GV; ++s) {
+      const unsigned long long bal = __ballot(v[s] != 0.0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int t0 = 64 * w + 16 * q;                    // the lane group's first thread
+        const int bit = ((t0 / PT + NG * s) >> 2) * MT + (t0 % PT) / 16;
+        wd |= ((unsigned)(bal >> (16 * q)) & 0xffffu) ? 1u << bit : 0u;
+      }
+    }
+    return prm.skip ? wd : ~0u;                            // skip off: every block runs
   };
   auto gen = [&](int rb, double (&v)[GV]) {
 #pragma unroll
@@ -310,6 +344,7 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
   auto store = [&](int buf, const double (&v)[GV]) {
 #pragma unroll
     for (int s = 0; s < GV; ++s) As[buf][g + NG * s][m] = v[s];
+    if constexpr (SKIP) Mk[buf][w] = mask_word(v);
   };
 
   const int li = lane & 15, lk = lane >> 4;
@@ -330,6 +365,13 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
     const int grb = (ks + LOOK) & (RXS - 1);
     double v[GV];
     double rr[RPT];
+    unsigned mk = ~0u;                                       // this K-step's activity bits (SGPR)
+    if constexpr (SKIP) {
+      mk = 0;
+#pragma unroll
+      for (int ww = 0; ww < NW; ++ww) mk |= Mk[buf][ww];
+      mk = __builtin_amdgcn_readfirstlane(mk);
+    }
     load_rows(ks + RA, rr);
     gen(grb, v);
 #pragma unroll
@@ -338,10 +380,12 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) af[mt] = As[buf][kk * 4 + lk][mt * 16 + li];
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
+      for (int mt = 0; mt < MT; ++mt) {
+        if (SKIP && !(mk & (1u << (kk * MT + mt)))) continue;   // an all-zero A fragment
 #pragma unroll
         for (int nt = T0; nt < T1c; ++nt)
           acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[mt], bb[(kk % BR) * NTW + nt], acc[mt][nt], 0, 0, 0);
+      }
       loadB_part(ks + (kk + BR) / 4, (kk + BR) % 4, kk % BR, bb);   // sub-step kk + BR
     }
     store(gslot, v);
@@ -742,7 +786,7 @@ void launch_obs_d(const TileParams& p, dim3 grid, hipStream_t stream) {
   const TileGeo g = p.geo;
   constexpr int kCoordVar = DI > 12 ? kTileCoordLDS : 0;   // (launch_d)
   if (g.mt == 2) {
-    hipLaunchKernelGGL((k_gp_tile<DI, false, kCoordVar | EF, 4, 2, 8>), grid, dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((k_gp_tile<DI, false, kCoordVar | kNoSkip32x512<DI> | EF, 4, 2, 8>), grid, dim3(256), 0, stream, p);
   } else if (g.mt == 1 && g.ntw == 8) {
     // 16-row tiles over the 32 x 512 image (small filters, capi_model.hip obs_pick; d <= 12)
     if constexpr (DI <= 12) hipLaunchKernelGGL((k_gp_tile<DI, false, EF, 4, 1, 8>), grid, dim3(256), 0, stream, p);
@@ -771,7 +815,7 @@ void launch_d(const TileParams& p, bool dyn, hipStream_t stream) {
     if (g.nw == 8)
       hipLaunchKernelGGL((k_gp_tile<DI, true, 0, 8>), grid, dim3(512), 0, stream, p);
     else if (g.mt == 2 && g.ntw == 8)
-      hipLaunchKernelGGL((k_gp_tile<DI, true, kCoordVar, 4, 2, 8>), grid, dim3(256), 0, stream, p);
+      hipLaunchKernelGGL((k_gp_tile<DI, true, kCoordVar | kNoSkip32x512<DI>, 4, 2, 8>), grid, dim3(256), 0, stream, p);
     else if (g.mt == 1)
       hipLaunchKernelGGL((k_gp_tile<DI, true, 0, 4, 1, 4>), grid, dim3(256), 0, stream, p);
     else

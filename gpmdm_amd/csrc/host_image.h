@@ -292,20 +292,29 @@ struct CutoffPacker {
 //  * each mean mu_j = sum_i k_i M_ij moves by at most tau |M_j|_1: tau_mu = min_j half an
 //    ulp of max_i |Y_ij| / |M_j|_1 (below the resolution of the training observations).
 // Returns min(tau_q, tau_mu).
-inline double obs_cutoff_tau(long long N, double sigma2, const double* M, int D, const double* y_absmax) {
+// |M_j|_1 for each of M's D columns (rows in order).
+inline std::vector<double> column_l1(long long N, const double* M, int D) {
+  std::vector<double> m1((size_t)D, 0.0);
+  for (int j = 0; j < D; ++j)
+    for (long long i = 0; i < N; ++i) m1[j] += std::fabs(M[i * D + j]);
+  return m1;
+}
+// ... from the column sums m1 = column_l1(M) (all of M that tau depends on)
+inline double obs_cutoff_tau_l1(long long N, double sigma2, const double* m1, int D, const double* y_absmax) {
   const double vc_min = sigma2 / ((double)N + sigma2);
   const double h = 0.5 * (std::nextafter(vc_min, 1.0) - vc_min);
   double tau = std::sqrt(sigma2) * h / (2.001 * std::sqrt((double)N));
   for (int j = 0; j < D; ++j) {
-    double m1 = 0.0;
-    for (long long i = 0; i < N; ++i) m1 += std::fabs(M[i * D + j]);
     const double yj = y_absmax[j];
-    if (m1 > 0.0 && yj > 0.0) {
-      const double t = 0.5 * (std::nextafter(yj, 1e308) - yj) / m1;
+    if (m1[j] > 0.0 && yj > 0.0) {
+      const double t = 0.5 * (std::nextafter(yj, 1e308) - yj) / m1[j];
       tau = t < tau ? t : tau;
     }
   }
   return tau;
+}
+inline double obs_cutoff_tau(long long N, double sigma2, const double* M, int D, const double* y_absmax) {
+  return obs_cutoff_tau_l1(N, sigma2, column_l1(N, M, D).data(), D, y_absmax);
 }
 
 }  // namespace gpmdm

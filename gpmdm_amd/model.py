@@ -466,8 +466,23 @@ class GPMDM(torch.nn.Module):
             h = ctypes.c_void_p()
             _lib.check(lib.gpmdm_model_create(ctypes.byref(desc), int(dev), ctypes.byref(h)), "gpmdm_model_create")
             self._extra_handles[dev] = h
+        self._install_obs_flush()
         if self._obs_cutoff:
             self._install_obs_cutoff()
+
+    def _obs_flush_args(self):
+        y_absmax = np.ascontiguousarray(np.max(np.abs(np.asarray(self.get_Y(), dtype=np.float64)), axis=0))
+        sigma2 = float(torch.exp(self._host("y_log_sigma_n"))) ** 2 + self.sigma_n_num_Y ** 2
+        return sigma2, y_absmax
+
+    def _install_obs_flush(self):
+        """The dense filter's flush threshold on every device image (gpmdm_model_set_obs_flush:
+        the cutoff's tau from the model's own K_y^-1 Y)."""
+        lib = _lib.load()
+        sigma2, y_absmax = self._obs_flush_args()
+        for h in [self._handle] + [self._extra_handles[d] for d in sorted(self._extra_handles)]:
+            _lib.check(lib.gpmdm_model_set_obs_flush(h, ctypes.c_double(sigma2), _lib.dptr(y_absmax)),
+                       "gpmdm_model_set_obs_flush")
 
     def _install_obs_cutoff(self):
         """The observation GP's cutoff image on every device image, built on the device from
@@ -475,8 +490,7 @@ class GPMDM(torch.nn.Module):
         the device image, K_y^-1 = U^-1 U^-T (gpmdm.py:1286-1290) by rocBLAS dsyrk, the
         tile-major packing by a device kernel; no N x N matrix on the host)."""
         lib = _lib.load()
-        y_absmax = np.ascontiguousarray(np.max(np.abs(np.asarray(self.get_Y(), dtype=np.float64)), axis=0))
-        sigma2 = float(torch.exp(self._host("y_log_sigma_n"))) ** 2 + self.sigma_n_num_Y ** 2
+        sigma2, y_absmax = self._obs_flush_args()
         for h in [self._handle] + [self._extra_handles[d] for d in sorted(self._extra_handles)]:
             _lib.check(lib.gpmdm_model_build_obs_cutoff(h, ctypes.c_double(sigma2), _lib.dptr(y_absmax), None, None),
                        "gpmdm_model_build_obs_cutoff")
@@ -509,6 +523,14 @@ class GPMDM(torch.nn.Module):
         """The cutoff tau of the model's cutoff image (0.0: none)."""
         t = ctypes.c_double()
         _lib.check(_lib.load().gpmdm_model_obs_cutoff(self.handle, ctypes.byref(t)), "gpmdm_model_obs_cutoff")
+        return t.value
+
+    @property
+    def obs_flush_tau(self) -> float:
+        """The tau below which the filters' observation likelihood flushes kernel values to 0
+        (0.0: the model flushes nothing; the predictive maps never do)."""
+        t = ctypes.c_double()
+        _lib.check(_lib.load().gpmdm_model_obs_flush(self.handle, ctypes.byref(t)), "gpmdm_model_obs_flush")
         return t.value
 
     def handle_on(self, device_index: int):

@@ -399,6 +399,7 @@ class GPMDM_PF:
         self._obs_cutoff = 3 if obs_cutoff == "auto" else (1 if obs_cutoff else 0)
         if obs_cutoff:
             gpmdm.enable_obs_cutoff(True)       # the model's cutoff image (built once)
+        self._obs_skip = True                   # set_obs_skip
 
         def create(model_handle, rank):
             h = ctypes.c_void_p()
@@ -413,6 +414,8 @@ class GPMDM_PF:
             _lib.check(lib.gpmdm_pf_set_dyn_tiles(h, _lib.DYN_TILES[dyn_tiles]), "dyn_tiles")
             if self._obs_cutoff:
                 _lib.check(lib.gpmdm_pf_set_obs_cutoff(h, self._obs_cutoff), "obs_cutoff")
+            if not self._obs_skip:
+                _lib.check(lib.gpmdm_pf_set_obs_skip(h, 0), "obs_skip")
             if self._smoothing_lag:
                 try:
                     _lib.check(lib.gpmdm_pf_set_smoothing(h, self._smoothing_lag), "smoothing_lag")
@@ -1099,6 +1102,15 @@ class GPMDM_PF:
             if split is not None:
                 _lib.check(lib.gpmdm_pf_set_obs_cutoff_split(h, self._CUT_SPLIT[split]), "set_obs_cutoff")
         self._obs_cutoff = mode
+
+    def set_obs_skip(self, on: bool = True):
+        """The dense observation tile branches around the MFMAs of all-zero 16 x 4 blocks of
+        kernel values (default) or runs every block (gpmdm_pf_set_obs_skip).  The results are
+        bitwise the same either way; off exists to show that.  Between frames only."""
+        lib = _lib.load()
+        for h in [self._h] + [p[0] for p in self._peers]:
+            _lib.check(lib.gpmdm_pf_set_obs_skip(h, 1 if on else 0), "set_obs_skip")
+        self._obs_skip = bool(on)
 
     def obs_cutoff_auto(self) -> dict:
         """AUTO cutoff state: whether the last frame ran the cutoff kernel, and the fraction of

@@ -427,6 +427,21 @@ int gpmdm_pf_obs_cutoff_stats(gpmdm_pf_t pf, int64_t* run, int64_t* dense, int r
 #define GPMDM_CUT_SPLIT_CHUNKS 4
 int gpmdm_pf_set_obs_cutoff_split(gpmdm_pf_t pf, int policy);
 
+/* The default (dense) filter's flush and block skip (DESIGN.md §3.4 "Flush and skip in the dense
+ * tile").  gpmdm_model_set_obs_flush computes the same tau as the cutoff image's, from the
+ * model's own K_y^-1 Y (sigma2, y_absmax: as gpmdm_model_set_obs_cutoff).  From then on the
+ * filters' observation likelihood replaces every kernel value below tau by exactly 0, value by
+ * value, so a particle's result depends on nothing but its own state; the predictive maps
+ * (gpmdm_predict_obs, gpmdm_predict_dyn) never flush.  A model without the call flushes nothing.
+ * gpmdm_model_obs_flush returns tau (0: none).  Between frames only.
+ * gpmdm_pf_set_obs_skip (default 1): the dense tile branches around the MFMAs of every 16-particle
+ * x 4-training-row block of kernel values that is exactly zero (flushed, underflowed or padding).
+ * Skipping such a block is bitwise the same as multiplying it; 0 runs every block in the same
+ * kernel with the same flush, so one process can hold the two against each other. */
+int gpmdm_model_set_obs_flush(gpmdm_model_t model, double sigma2, const double* y_absmax);
+int gpmdm_model_obs_flush(gpmdm_model_t model, double* tau);
+int gpmdm_pf_set_obs_skip(gpmdm_pf_t pf, int on);
+
 /* Failure detection.  The filter keeps the reference's arithmetic: a
  * non-positive predictive variance gives NaN log-likelihoods / states as it does in
  * gpmdm_pf.py:167-168, 188-192.  Each event is counted on the device (per particle and
