@@ -68,16 +68,36 @@ static __constant__ double kExp2Tab[64] = {
 // polynomial in f (|f| <= 1/2, truncation < 2^-55), table 2^(j/64), ldexp.  No clamp is
 // needed: v_cvt_i32_f64 saturates and ldexp underflows to 0 exactly like exp().
 
+// The chain in three stages, so that the K loop can state them apart (k_gp_tile full_step);
+// exp2_64 is the three in a row.
+struct Exp2Mid {
+  double f, p;                                                      // f; the polynomial so far
+  int ni;
+};
+__device__ __forceinline__ Exp2Mid exp2_64_head(double t);          // n, f, the first two fmas
+__device__ __forceinline__ double exp2_64_poly(const Exp2Mid& h);   // 2^(f/64) - 1
+__device__ __forceinline__ double exp2_64_scale(double tj, double p, int ni);
+
 __device__ __forceinline__ double exp2_64(double t, const double* tab) {
+  const Exp2Mid h = exp2_64_head(t);
+  const double p = exp2_64_poly(h);
+  return exp2_64_scale(tab[h.ni & 63], p, h.ni);
+}
+__device__ __forceinline__ Exp2Mid exp2_64_head(double t) {
   const double n = __builtin_rint(t);
   const double f = t - n;
   double p = fma(f, 1.2417843701716925e-12, 5.732851688640402e-10);
   p = fma(p, f, 2.1173137155464776e-07);
+  return Exp2Mid{f, p, (int)n};
+}
+__device__ __forceinline__ double exp2_64_poly(const Exp2Mid& h) {
+  const double f = h.f;
+  double p = h.p;
   p = fma(p, f, 5.86490495505617e-05);
   p = fma(p, f, 0.010830424696249145);
-  p *= f;                                                          // 2^(f/64) - 1
-  const int ni = (int)n;
-  const double tj = tab[ni & 63];
+  return p * f;                                                    // 2^(f/64) - 1
+}
+__device__ __forceinline__ double exp2_64_scale(double tj, double p, int ni) {
   return ldexp(fma(tj, p, tj), ni >> 6);
 }
 
@@ -95,8 +115,11 @@ __device__ __forceinline__ double exp2_64(double t, const double* tab) {
 // row of each particle's filter: the instantiations only a masked bank launches, so every
 // other launch runs the epilogue with one row, unchanged.
 // kTileNoSkip -- the K loop runs every MFMA (no activity words, no branch): the shapes whose
-// register budget cannot take the branch without spilling (kNoSkip32x512).  The flush is the same
-// either way, so the values are too.
+// register budget cannot take the branch without spilling (kNoSkip32x512), and the dynamics GP's
+// 16 x 256 and (d <= 12) 32 x 512 shapes: dynamics rows never flush, so the branch could skip
+// padding only, and it cost the narrow tile 5% of its launch.  (The 64-row dynamics shapes and
+// 32 x 512 above d = 12 keep it: without it they spill, tools/tile_resources.py.)  The flush is
+// the same either way, so the values are too.
 constexpr int kTileCoordLDS = 131072;
 constexpr int kTileLamRows = 262144;
 constexpr int kTileNoSkip = 524288;
@@ -104,6 +127,8 @@ constexpr int kTileNoSkip = 524288;
 // it spills 14 - 16 VGPRs into the K loop (tools/tile_resources.py), so it runs without it.
 template <int DI>
 constexpr int kNoSkip32x512 = (DI == 11 || DI == 12) ? kTileNoSkip : 0;
+template <int DI>
+constexpr int kDynNoSkip32x512 = DI <= 12 ? kTileNoSkip : 0;
 template <int I, int E, class F>
 __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (I < E) {
@@ -167,6 +192,7 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
   constexpr int NHS = (DYN && NW == 4 && NTW == 8) ? 2 : 1;
   __shared__ double qred[NHS * NW][PT];
   constexpr bool PLDS = (FLAGS & kTileCoordLDS) != 0;
+  constexpr bool kPlainStep = PLDS || DI > 16;                         // (full_step)
   __shared__ double PA[PLDS ? PT : 1][PLDS ? DI + 1 : 1];
   __shared__ double sred[NHS * NW][PT];
 
@@ -307,20 +333,33 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
     const double e = exp2_64(x, tab);                      // padding rows: exactly 0
     return x < t_flush ? 0.0 : e;                          // the flush: below tau, exactly 0
   };
-  // this wave's activity word for the values it generated (lanes 16 q .. 16 q + 15 share a row
-  // block and a training row: wave-uniform arithmetic on the compare's lane mask)
+  // this wave's activity word for the values it generated.  Lanes 16 q .. 16 q + 15 share a row
+  // block and a training row, and lane groups q and q + NF share their bit (their rows lie in one
+  // sub-step), so a value sets NF flags: each one test of the compare's lane mask against a
+  // constant and a select of the flag's bit, which is wave-uniform and the same for every K-step
+  // (a shift, a mask, a compare, a select and an OR per lane group before: 40 SALU per K-step
+  // of the 32 x 512 shape against 17, all of them behind the K-step's last MFMA).
+  constexpr int NF = PT / 16 < 4 ? PT / 16 : 4;
+  unsigned fbit[GV][NF];
+#pragma unroll
+  for (int s = 0; s < GV; ++s)
+#pragma unroll
+    for (int q = 0; q < NF; ++q) {
+      const int t0 = 64 * w + 16 * q;                      // the lane group's first thread
+      fbit[s][q] = 1u << (((t0 / PT + NG * s) >> 2) * MT + (t0 % PT) / 16);
+    }
+  auto mask_bits = [&](int s, double vs) -> unsigned {
+    constexpr unsigned long long kGroups = NF == 1 ? ~0ull : NF == 2 ? 0x0000ffff0000ffffull : 0xffffull;
+    const unsigned long long bal = __ballot(vs != 0.0);
+    unsigned wd = 0;
+#pragma unroll
+    for (int q = 0; q < NF; ++q) wd |= (bal & (kGroups << (16 * q))) ? fbit[s][q] : 0u;
+    return wd;
+  };
   auto mask_word = [&](const double (&v)[GV]) -> unsigned {
     unsigned wd = 0;
 #pragma unroll
-    for (int s = 0; s < GV; ++s) {
-      const unsigned long long bal = __ballot(v[s] != 0.0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int t0 = 64 * w + 16 * q;                    // the lane group's first thread
-        const int bit = ((t0 / PT + NG * s) >> 2) * MT + (t0 % PT) / 16;
-        wd |= ((unsigned)(bal >> (16 * q)) & 0xffffu) ? 1u << bit : 0u;
-      }
-    }
+    for (int s = 0; s < GV; ++s) wd |= mask_bits(s, v[s]);
     return prm.skip ? wd : ~0u;                            // skip off: every block runs
   };
   auto gen = [&](int rb, double (&v)[GV]) {
@@ -357,12 +396,12 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
   // One K-step with tiles [T0, T1) active: generate K*(ks+LOOK) and stage rows(ks+RA), then
   // per sub-step kk: A fragments from LDS, MFMAs, refill B(ks+1) for kk.  (Generating past
   // the last K-step is harmless: clamped rows, stored to a slot never read again.)
-  auto full_step = [&](auto t0c, auto t1c, int ks, double (&bb)[BR * NTW]) {
+  // plain_step: kTileNoSkip, where every MFMA runs and the compiler schedules the K-step as one
+  // block, and the shapes that cannot take full_step's order below without spilling more than
+  // before (kPlainStep: 32 x 512 with the coordinates in LDS, and d > 16), which branch as well.
+  auto plain_step = [&](auto t0c, auto t1c, int ks, double (&bb)[BR * NTW]) {
     constexpr int T0 = decltype(t0c)::value, T1c = decltype(t1c)::value;
     const int buf = ks & (ASL - 1);
-    const int gslot = (ks + LOOK) & (ASL - 1);
-    const int rslot = (ks + RA) & (RXS - 1);
-    const int grb = (ks + LOOK) & (RXS - 1);
     double v[GV];
     double rr[RPT];
     unsigned mk = ~0u;                                       // this K-step's activity bits (SGPR)
@@ -373,7 +412,7 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
       mk = __builtin_amdgcn_readfirstlane(mk);
     }
     load_rows(ks + RA, rr);
-    gen(grb, v);
+    gen((ks + LOOK) & (RXS - 1), v);
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
       double af[MT];
@@ -388,9 +427,79 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
       }
       loadB_part(ks + (kk + BR) / 4, (kk + BR) % 4, kk % BR, bb);   // sub-step kk + BR
     }
-    store(gslot, v);
-    store_rows(rslot, rr);
+    store((ks + LOOK) & (ASL - 1), v);
+    store_rows((ks + RA) & (RXS - 1), rr);
     if (ks % SB == SB - 1) __syncthreads();
+  };
+  // With the branch around all-zero fragments the K-step's 4 MT fragments (kk, mt) are basic
+  // blocks of their own and the compiler moves nothing between them.  The generation stands in
+  // front of the first branch, value by value in gen_one's arithmetic, each value stored to its
+  // K* slot and its activity flags taken as soon as it exists (the slot is not read before the
+  // next barrier); the word's store and the staged rows follow the last fragment.  This order
+  // measured fastest of those tried (profiles/obs_overlap/README.md).
+  auto full_step = [&](auto t0c, auto t1c, int ks, double (&bb)[BR * NTW]) {
+    if constexpr (!SKIP || kPlainStep) {
+      plain_step(t0c, t1c, ks, bb);
+    } else {
+      constexpr int T0 = decltype(t0c)::value, T1c = decltype(t1c)::value;
+      const int buf = ks & (ASL - 1);
+      const int gslot = (ks + LOOK) & (ASL - 1);
+      const int grb = (ks + LOOK) & (RXS - 1);
+      double rr[RPT];
+      double af[2][MT];
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) af[0][mt] = As[buf][lk][mt * 16 + li];
+      unsigned mk = 0;                                         // this K-step's activity bits (SGPR)
+#pragma unroll
+      for (int ww = 0; ww < NW; ++ww) mk |= Mk[buf][ww];
+      mk = __builtin_amdgcn_readfirstlane(mk);
+      load_rows(ks + RA, rr);
+      double gx = 0.0, gp = 0.0, gtj = 0.0;                    // the value in flight
+      Exp2Mid gh{0.0, 0.0, 0};
+      unsigned wd = 0;
+      auto piece = [&](auto ic) {
+        constexpr int i = decltype(ic)::value, s = i / 4;
+        if constexpr (i % 4 == 0) {
+          const double* row = &RX[grb][(g + NG * s) * RW];
+          gx = -(asq + row[DI]);
+#pragma unroll
+          for (int j = 0; j < DI; ++j) gx = fma(PLDS ? PA[m][j] : a2[j], row[j], gx);
+        } else if constexpr (i % 4 == 1) {
+          gh = exp2_64_head(gx);
+          gtj = tab[gh.ni & 63];
+        } else if constexpr (i % 4 == 2) {
+          gp = exp2_64_poly(gh);
+        } else {
+          const double e = exp2_64_scale(gtj, gp, gh.ni);      // padding rows: exactly 0
+          const double vs = gx < t_flush ? 0.0 : e;            // the flush: below tau, exactly 0
+          As[gslot][g + NG * s][m] = vs;
+          wd |= mask_bits(s, vs);
+        }
+      };
+      static_for<0, 4 * GV>([&](auto ic) { piece(ic); });
+      static_for<0, 4>([&](auto kkc) {
+        constexpr int kk = decltype(kkc)::value;
+        if constexpr (kk > 0) {
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) af[kk & 1][mt] = As[buf][kk * 4 + lk][mt * 16 + li];
+        }
+        static_for<0, MT>([&](auto mtc) {
+          constexpr int mt = decltype(mtc)::value;
+          constexpr int fr = kk * MT + mt;
+          if (!(mk & (1u << fr))) {                            // an all-zero A fragment
+          } else {
+            acc[mt][T0] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kk & 1][mt], bb[(kk % BR) * NTW + T0], acc[mt][T0], 0, 0, 0);
+#pragma unroll
+            for (int nt = T0 + 1; nt < T1c; ++nt)
+              acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kk & 1][mt], bb[(kk % BR) * NTW + nt], acc[mt][nt], 0, 0, 0);
+          }
+        });
+        loadB_part(ks + (kk + BR) / 4, (kk + BR) % 4, kk % BR, bb);   // sub-step kk + BR
+      });
+      Mk[gslot][w] = prm.skip ? wd : ~0u;                      // skip off: every block runs
+      store_rows((ks + RA) & (RXS - 1), rr);
+      if (ks % SB == SB - 1) __syncthreads();
+    }
   };
   double bb[BR * NTW];
   {
@@ -811,13 +920,14 @@ void launch_d(const TileParams& p, bool dyn, hipStream_t stream) {
   constexpr int kCoordVar = DI > 12 ? kTileCoordLDS : 0;
   if (dyn) {
     // dynamics images: narrow 16 x 256, wide = the observation GP's shape, or a model-wide
-    // tile_shape (64 x 256 / 64 x 512)
+    // tile_shape (64 x 256 / 64 x 512); the first two without the branch where that costs no
+    // spill (kTileNoSkip)
     if (g.nw == 8)
       hipLaunchKernelGGL((k_gp_tile<DI, true, 0, 8>), grid, dim3(512), 0, stream, p);
     else if (g.mt == 2 && g.ntw == 8)
-      hipLaunchKernelGGL((k_gp_tile<DI, true, kCoordVar | kNoSkip32x512<DI>, 4, 2, 8>), grid, dim3(256), 0, stream, p);
+      hipLaunchKernelGGL((k_gp_tile<DI, true, kCoordVar | kDynNoSkip32x512<DI>, 4, 2, 8>), grid, dim3(256), 0, stream, p);
     else if (g.mt == 1)
-      hipLaunchKernelGGL((k_gp_tile<DI, true, 0, 4, 1, 4>), grid, dim3(256), 0, stream, p);
+      hipLaunchKernelGGL((k_gp_tile<DI, true, kTileNoSkip, 4, 1, 4>), grid, dim3(256), 0, stream, p);
     else
       hipLaunchKernelGGL((k_gp_tile<DI, true, 0, 4>), grid, dim3(256), 0, stream, p);
   } else if (p.lam_ld) {
