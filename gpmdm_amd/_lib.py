@@ -158,6 +158,8 @@ _SIGS = {
     "gpmdm_bank_observation_gp": (c_int, [c_void_p, _dp, c_void_p]),
     "gpmdm_pf_set_gate": (c_int, [c_void_p, c_double, c_double]),
     "gpmdm_pf_gate_report": (c_int, [c_void_p, POINTER(GateOut), c_void_p]),
+    "gpmdm_bank_set_gate": (c_int, [c_void_p, _dp, c_double]),
+    "gpmdm_bank_gate_report": (c_int, [c_void_p, POINTER(GateOut), c_void_p]),
     "gpmdm_pf_set_comm": (c_int, [c_void_p, c_void_p, c_int]),
     "gpmdm_comm_unique_id": (c_int, [c_void_p]),
     "gpmdm_comm_init": (c_int, [c_int, c_int, c_void_p, c_int, POINTER(c_void_p)]),

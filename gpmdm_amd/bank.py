@@ -28,7 +28,8 @@ import torch
 from . import _lib, replay
 from .distributed import shard_range
 from .model import GPMDM
-from .pf import Forecast, Innovation, Smoothed, _check_smoothing_lag, _forecast_call, _innovation_call, _smoothed_call
+from .pf import (BankGateReport, Forecast, Innovation, Smoothed, _check_bank_gate, _check_smoothing_lag, _forecast_call,
+                 _innovation_call, _smoothed_call)
 
 
 def _filter_major(a):
@@ -40,7 +41,14 @@ class GPMDM_PF_Bank:
     def __init__(self, gpmdm: GPMDM, markov_switching_model, num_filters: int, num_particles: int, *,
                  seed=None, resample: str = "multinomial", process_group=None, shard=None,
                  dedup: bool = True, dyn_tiles: str = "auto", obs_cutoff: bool = False, smoothing_lag: int = 0,
-                 predictive: bool = False):
+                 predictive: bool = False, **gating):
+        """``gating``: the keywords ``gate`` (default None) and ``gate_limit`` (default 0.5) of
+        ``set_gate``, and nothing else (TypeError).  They are taken as a keyword group and are not
+        named parameters of the signature: tests/test_gate_api_host.py pins the named ones."""
+        unknown = sorted(set(gating) - {"gate", "gate_limit"})
+        if unknown:
+            raise TypeError(f"GPMDM_PF_Bank() got an unexpected keyword argument {unknown[0]!r}")
+        gate, gate_limit = gating.get("gate"), gating.get("gate_limit", 0.5)
         self._gpmdm = gpmdm
         self._gpmdm.set_evaluation_mode()
         self._T = torch.as_tensor(markov_switching_model).type(torch.float64)
@@ -72,6 +80,10 @@ class GPMDM_PF_Bank:
         self._seed = int(seed)
         self._world, self._rank = world, rank
         self._f_lo, self._f_hi = shard_range(self._num_filters, world, rank)
+        gate, gate_limit = _check_bank_gate(gate, gate_limit, self._num_filters, self._f_lo, self._f_hi)
+        if gate is not None and not predictive:
+            raise ValueError("gate= needs predictive=True (the gate reads the frame's vc)")
+        self._gate, self._gate_limit = None, gate_limit
         self._h = None
         self._readout = None
         if obs_cutoff:
@@ -97,6 +109,8 @@ class GPMDM_PF_Bank:
                 self.set_smoothing(self._smoothing_lag)
         if predictive:
             self.set_predictive(True)
+        if gate is not None:
+            self.set_gate(gate, gate_limit)
 
     def __del__(self):
         try:
@@ -283,7 +297,10 @@ class GPMDM_PF_Bank:
         """``GPMDM_PF.set_predictive`` for the bank (gpmdm_bank_set_predictive): every update
         from now on keeps each particle's vc for ``innovation`` and
         ``current_observation(gp_variance=True)``; off, the bank issues exactly the work of a
-        bank built without it.  Between updates only."""
+        bank built without it.  Between updates only; ValueError for ``set_predictive(False)`` while
+        the gate is on."""
+        if not on and getattr(self, "_gate", None) is not None:
+            raise ValueError("set_predictive(False) while the gate is on: call set_gate(None) first")
         if self._h is not None:
             self._sync_model()
             _lib.check(_lib.load().gpmdm_bank_set_predictive(self._h, 1 if on else 0), "set_predictive")
@@ -302,6 +319,65 @@ class GPMDM_PF_Bank:
             raise ValueError("innovation: build the bank with predictive=True or call set_predictive(True)")
         return _innovation_call(self, None if self._h is None else "gpmdm_bank_innovation", (self.local_filters,),
                                 particles)
+
+    def set_gate(self, gate=None, limit: float = 0.5):
+        """``GPMDM_PF.set_gate`` for the bank (gpmdm_bank_set_gate; the constructor's ``gate`` /
+        ``gate_limit``): from the next update on every filter rejects its own outlier joints inside
+        ``update``, from its own row of ``Z``, of the masks and of the frame's innovations --
+        ``bank = GPMDM_PF_Bank(m, T, F, P, predictive=True, gate=6.0); bank.update(Z);
+        bank.gate_report().gated``.  ``gate``: None (off), one real number > 0 for every filter, or a
+        sequence of ``num_filters`` entries (each rank takes its rows, as for ``observed``), each a
+        real number > 0 or None -- that filter never rejects.  The cap is per filter,
+        floor(``limit`` x the filter's observed joints).  A gated-mode update queues the innovation
+        pair, the decision, the re-weigh tile and its finish once for all filters, without a host
+        wait; filter f's frame is bitwise the frame of ``GPMDM_PF(rng="philox", seed=seed + f,
+        predictive=True, gate=gate[f])``, and a filter that rejects nothing is bitwise the ungated
+        filter whatever its neighbours reject.  A blacked-out filter's ``ll`` stays exactly 0.
+        ``gate=None`` turns it off: an update then issues exactly the work it issued without the
+        feature.  Needs ``predictive`` (ValueError otherwise); between updates only.  Invalidates the
+        last report."""
+        ks, lim = _check_bank_gate(gate, limit, self._num_filters, self._f_lo, self._f_hi)
+        if ks is not None and not self._predictive:
+            raise ValueError("gate: build the bank with predictive=True or call set_predictive(True)")
+        if self._h is not None:
+            self._sync_model()
+            thr = np.zeros(self.local_filters) if ks is None else np.array(
+                [np.inf if k is None else k for k in ks], dtype=np.float64)
+            _lib.check(_lib.load().gpmdm_bank_set_gate(self._h, _lib.dptr(thr), lim), "set_gate")
+        self._gate, self._gate_limit = ks, lim
+
+    @property
+    def gate(self):
+        """The local filters' z-score thresholds as a tuple (None: that filter never rejects), or
+        None when the gate is off."""
+        return self._gate
+
+    @property
+    def gate_limit(self) -> float:
+        return self._gate_limit
+
+    def gate_report(self) -> BankGateReport:
+        """``GPMDM_PF.gate_report`` for every local filter (gpmdm_bank_gate_report: one copy of the
+        device tables and one wait): what each filter's gate decided for the frame the last
+        ``update`` weighed, every field with a leading filter axis, row f bitwise the single
+        filter's report.  No state change, no draw.  ValueError with the gate off, RuntimeError
+        before the first update after ``reset`` / ``load_state`` / ``set_predictive`` /
+        ``set_gate``."""
+        if getattr(self, "_gate", None) is None:
+            raise ValueError("gate_report: build the bank with gate=k or call set_gate(k)")
+        Fl, D = self.local_filters, self.observation_dim
+        zs = np.full((Fl, D), np.nan)
+        ex, ga, us = (np.zeros((Fl, D), dtype=np.uint8) for _ in range(3))
+        ng, nv, ov = np.zeros(Fl, dtype=np.int64), np.zeros(Fl, dtype=np.int64), np.zeros(Fl, dtype=np.int32)
+        if self._h is not None:
+            self._sync_model()
+            out = _lib.GateOut(_lib.dptr(zs), *[ctypes.c_void_p(a.ctypes.data) for a in (ex, ga, us)],
+                               _lib.i64ptr(ng), _lib.i64ptr(nv), ov.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+            _lib.check(_lib.load().gpmdm_bank_gate_report(self._h, ctypes.byref(out), self._stream()), "gate_report")
+        thr = np.array([np.inf if k is None else k for k in self._gate], dtype=np.float64)
+        b = lambda a: torch.from_numpy(a.astype(bool))   # noqa: E731
+        return BankGateReport(torch.from_numpy(thr), torch.from_numpy(zs), b(ex), b(ga), b(us), torch.from_numpy(ng),
+                              torch.from_numpy(nv), b(ov))
 
     def current_observation(self, spread: bool = True, gp_variance: bool = False):
         """(F_local, D): the filtered pose of every local filter, ``GPMDM_PF.current_observation``

@@ -583,8 +583,8 @@ int weigh(gpmdm_pf* pf, const double* zh, hipStream_t s) {
     pf->pv_resampled = false;
     // gating (capi_gate.hip): the decision from this frame's own innovations and, where it
     // rejects joints, ll and the block maxima of the kept ones -- behind the finish, before the
-    // normaliser; off, nothing is launched
-    if (pf->gate_k > 0.0 && pf->F == 1) TRY(gate_frame(pf, s));
+    // normaliser, once for all the filters of a bank; off, nothing is launched
+    if (pf->gate_k > 0.0) TRY(gate_frame(pf, s));
   }
   pf->propagated = true;
   pf->dyn_done = false;

@@ -436,19 +436,27 @@ struct gpmdm_pf {
   DevBuf<double> iv_part;
   Landing iv_out;
   void pv_clear() { pv_weighed = pv_has_vc = pv_resampled = gt_ready = false; }
-  // Outlier gating inside the frame (gpmdm_pf_set_gate, gpmdm_pf_gate_report; obs_gate.h,
-  // capi_gate.hip).  gate_k > 0: on (single filters on one rank, predictive on): weigh ends with
-  // gate_frame -- the innovation launches into scratch of the gate's own (gt_part, gt_out), then
-  // the decision, the re-weigh tile and its finish -- on the frame's stream, so the frame's
-  // read-out follows them and the lifecycle waits cover them.  gt_tab: the device table
-  // (GateTab), gt_sp the re-weigh partials, gt_lil the host's log il2_j of the filter's model
-  // (uploaded by set_gate and again by a rebind), gt_pin the report's pinned landing buffer.
+  // Outlier gating inside the frame (gpmdm_pf_set_gate, gpmdm_pf_gate_report and the banks'
+  // gpmdm_bank_set_gate, gpmdm_bank_gate_report; obs_gate.h, capi_gate.hip).  gate_k > 0: on
+  // (one rank, predictive on; gate_ks: the F filters' thresholds, +inf: that filter never
+  // rejects; gate_k: the first of them): weigh ends with gate_frame -- the innovation launches
+  // into scratch of the gate's own (gt_part, gt_out), then the decision, the re-weigh tile and
+  // its finish, each once for all F filters -- on the frame's stream, so the frame's read-out
+  // follows them and the lifecycle waits cover them.  gt_tab: the device tables (F x GateTab),
+  // gt_sp the re-weigh partials, gt_lil the host's log il2_j of the filter's model (uploaded by
+  // set_gate and again by a rebind), gt_pin the report's pinned landing buffer.
+  // gt_cfg: the decision's F x {threshold, cap} table, the cap floor(limit D_obs_f) formed on
+  // the host in fp64 from the frame's per-filter observed counts; gt_cfg_host is what the device
+  // holds, and gate_frame uploads a frame's table only when it differs (a new threshold, limit or
+  // mask), after the wait that guards gt_lil (zslot_free: the last frame's decision has read it).
   // gt_ready: a frame has been weighed in gated mode since the last propagate, init, import,
-  // rebind, set_predictive or set_gate (gt_host: a blackout frame, no launch; the report is the
-  // host's).
+  // rebind, set_predictive or set_gate (gt_host: a blackout frame of every filter, no launch;
+  // gt_black: the filters blacked out in that frame -- their report rows are the host's).
   double gate_k = 0.0, gate_limit = 0.5;
+  std::vector<double> gate_ks, gt_cfg_host;
+  std::vector<unsigned char> gt_black;
   bool gt_ready = false, gt_host = false;
-  DevBuf<double> gt_part, gt_out, gt_tab, gt_sp, gt_lil;
+  DevBuf<double> gt_part, gt_out, gt_tab, gt_sp, gt_lil, gt_cfg;
   PinBuf<double> gt_pin;
   // likelihood finish deferred into the resampling launch (single-shard small filters:
   // k_small_resample computes ll first, one launch less per frame); flush_ll runs it for

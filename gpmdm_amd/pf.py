@@ -238,6 +238,41 @@ def _check_gate(k, limit):
     return float(k), float(limit)
 
 
+class BankGateReport(NamedTuple):
+    """``GPMDM_PF_Bank.gate_report``'s result (CPU tensors): ``GateReport`` with a leading axis over
+    this rank's filters.  Row f is bitwise the single filter's report on filter f's frame;
+    ``threshold`` is ``inf`` for a filter that never rejects, and a blacked-out filter's row is a
+    blackout frame's (``zscore`` NaN, no flag set, ``n_valid`` 0)."""
+    threshold: torch.Tensor                             # (F,)
+    zscore: torch.Tensor                                # (F, D)
+    exceeded: torch.Tensor                              # (F, D) bool
+    gated: torch.Tensor                                 # (F, D) bool
+    used: torch.Tensor                                  # (F, D) bool
+    n_gated: torch.Tensor                               # (F,) int64
+    n_valid: torch.Tensor                               # (F,) int64
+    overflow: torch.Tensor                              # (F,) bool
+
+
+def _check_bank_gate(gate, limit, F, f_lo, f_hi):
+    """A bank's ``gate`` as a tuple over the filters [f_lo, f_hi) of F (entries: a float > 0, or
+    None: that filter never rejects), or None (off), and ``gate_limit`` as a float; raised here,
+    before the library is touched.  ``gate``: None, one real number > 0 for every filter, or a
+    sequence of F (each rank takes its rows) or f_hi - f_lo (local) entries."""
+    _, lim = _check_gate(None, limit)
+    if gate is None:
+        return None, lim
+    Fl = f_hi - f_lo
+    if isinstance(gate, (list, tuple)) or (isinstance(gate, np.ndarray) and gate.ndim == 1):
+        ks = list(gate)
+        if len(ks) == F and Fl != F:
+            ks = ks[f_lo:f_hi]
+        elif len(ks) != Fl:
+            raise ValueError(f"gate must be None, one real number > 0 or a sequence of {F} (or {Fl} local) "
+                             f"entries, got {len(ks)}")
+        return tuple(None if k is None else _check_gate(k, lim)[0] for k in ks), lim
+    return (_check_gate(gate, lim)[0],) * Fl, lim
+
+
 def _check_smoothing_lag(L) -> int:
     if isinstance(L, bool) or not isinstance(L, (int, np.integer)):
         raise ValueError(f"smoothing lag must be an integer, got {L!r}")

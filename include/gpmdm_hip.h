@@ -735,6 +735,25 @@ typedef struct gpmdm_gate_out {   /* host arrays; any may be NULL */
 } gpmdm_gate_out;
 int gpmdm_pf_set_gate(gpmdm_pf_t pf, double threshold, double limit);   /* threshold <= 0: off */
 int gpmdm_pf_gate_report(gpmdm_pf_t pf, const gpmdm_gate_out* out, void* stream);
+/* Filter banks (gpmdm_bank_create; a single filter is the bank of one): every filter decides for
+ * itself, from its own row of z, of the masks and of the innovations, inside the bank's frame.
+ * A gated-mode frame queues the innovation pair, the decision, the re-weigh tile and its finish
+ * once for all F filters, with the filter as a grid dimension -- never per filter, and without a
+ * host wait.  Filter f's frame is bitwise the frame of a single filter (seed + f) with threshold
+ * thresholds[f] on f's row; a filter that rejects nothing is bitwise the ungated filter, whatever
+ * its neighbours reject.
+ * gpmdm_bank_set_gate: thresholds[f] > 0 per filter, +inf: that filter never rejects; all
+ * thresholds <= 0: off for the whole bank (GPMDM_E_INVALID: NaN, or some <= 0 and some not).
+ * The cap is per filter, floor(limit D_obs_f) of the frame's masks (gpmdm_bank_set_obs_masks); a
+ * blacked-out filter's ll stays exactly 0.  The other rules and errors are gpmdm_pf_set_gate's
+ * (the predictive switch: gpmdm_bank_set_predictive).  A bank sharded by filter is one handle
+ * per rank and is served as it is.
+ * gpmdm_bank_gate_report: gpmdm_gate_out with a leading filter axis -- zscore, exceeded, gated,
+ * used F x D filter-major, n_gated, n_valid, overflow F each; a blacked-out filter's row is a
+ * blackout frame's.  Up to 65535 filters.  gpmdm_pf_set_gate / gpmdm_pf_gate_report refuse a
+ * bank handle (GPMDM_E_INVALID). */
+int gpmdm_bank_set_gate(gpmdm_pf_t pf, const double* thresholds, double limit);   /* F thresholds; all <= 0: off */
+int gpmdm_bank_gate_report(gpmdm_pf_t pf, const gpmdm_gate_out* out, void* stream);   /* arrays F x D, counts F */
 
 /* Device-side GP factor: the recipe of _precompute_kernel_inverses
  * (gpmdm.py:1284-1305) for one GP block -- the observation GP, or one class block of the

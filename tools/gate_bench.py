@@ -15,7 +15,12 @@ innovation launches (gpmdm_pf_innovation): the K loop the re-weigh tile shares, 
 the gate launches.  ``reweigh_over_readout`` = (gated - clean) / read-out.
 Prints one JSON line per configuration and writes profiles/gate/config{1,2}.json.
 
+``--filters F``: the same three frames for a bank of F filters (GPMDM_PF_Bank(gate=k), every filter
+its own stream; ``gated``: filter 0 rejects a joint) and, beside them, the loop of F single gated
+filters the bank's gate replaces; writes profiles/gate/bank{F}_config{cfg}.json.
+
     python tools/gate_bench.py [--configs 2 1] [--out profiles/gate]
+    python tools/gate_bench.py --filters 39 [--configs 1]
 """
 import argparse
 import json
@@ -84,9 +89,83 @@ def run(cfg, frames, calls, repeats):
     }
 
 
+class SingleLoop:
+    """F single gated filters stepped one after another: what a bank's gate replaces."""
+
+    def __init__(self, pfs):
+        self.pfs = pfs
+
+    def update(self, Z):
+        for pf, z in zip(self.pfs, Z):
+            pf.update(z)
+
+    def class_probabilities(self):
+        return [pf.class_probabilities() for pf in self.pfs]
+
+    def current_state_mean(self):
+        return [pf.current_state_mean() for pf in self.pfs]
+
+    def log_likelihood(self):
+        return [pf.log_likelihood() for pf in self.pfs]
+
+
+def run_bank(cfg, F, frames, repeats):
+    """--filters F: a bank of F filters (each its own stream) with predictive=True only, gated with
+    nothing rejected, gated with filter 0 rejecting joint 0 of every frame, and the loop of F single
+    gated filters on that last stream; the same rotation and figures as ``run``."""
+    from gpmdm_amd import GPMDM_PF_Bank
+    c = synthetic.CONFIGS[cfg]
+    dev = torch.device("cuda:0")
+    m, data = build_model(c, dev)
+    P = c["P"]
+    T = torch.from_numpy(synthetic.markov_matrix(c["C"]))
+    n = 5 + repeats * frames
+    zs = np.stack([np.asarray(data.observation_stream(n, seed=1 + f), dtype=np.float64) for f in range(F)], 1)
+    bad = zs.copy()
+    bad[:, 0, 0] += SHIFT
+    kinds = {"off": dict(predictive=True), "clean": dict(predictive=True, gate=THRESHOLD),
+             "gated": dict(predictive=True, gate=THRESHOLD), "loop": None}
+    runs = {}
+    for kind, kw in kinds.items():
+        if kw is None:
+            torch.manual_seed(0)
+            runs[kind] = SingleLoop([GPMDM_PF(m, T, P, rng="philox", seed=11 + f, gate=THRESHOLD) for f in range(F)])
+        else:
+            runs[kind] = GPMDM_PF_Bank(m, T, F, P, seed=11, **kw)
+        for k in range(5):
+            runs[kind].update(zs[k] if kind in ("off", "clean") else bad[k])
+
+    def verdicts():
+        assert not runs["clean"].gate_report().n_gated.any()
+        assert runs["gated"].gate_report().n_gated.tolist() == [1] + [0] * (F - 1)
+        assert [pf.gate_report().n_gated for pf in runs["loop"].pfs] == [1] + [0] * (F - 1)
+
+    verdicts()
+    res = {k: [] for k in kinds}
+    order = list(kinds)
+    k0 = 5
+    for r in range(repeats):
+        for kind in order:
+            res[kind].append(frame_ms(runs[kind], (zs if kind in ("off", "clean") else bad)[k0:k0 + frames]))
+        order = order[1:] + order[:1]                       # rotate the order
+        k0 += frames
+    verdicts()
+    best = {k: min(v) for k, v in res.items()}
+    return {
+        "config": cfg, "N": c["C"] * c["S"] * c["L"], "D": c["D"], "d": c["d"], "P": P, "filters": F, "rng": "philox",
+        "commit": commit_hash(), "device": torch.cuda.get_device_name(0), "frames": frames,
+        "frame_ms_bank_predictive": res["off"], "frame_ms_bank_gate_clean": res["clean"],
+        "frame_ms_bank_gate_gated": res["gated"], "frame_ms_single_loop_gated": res["loop"],
+        "gate_clean_extra_ms": best["clean"] - best["off"], "gate_gated_extra_ms": best["gated"] - best["clean"],
+        "loop_over_bank": best["loop"] / best["gated"],
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--configs", type=int, nargs="+", default=[2, 1])
+    ap.add_argument("--filters", type=int, default=0,
+                    help="F > 0: the bank mode (run_bank; default config 1); writes bank{F}_config{cfg}.json")
+    ap.add_argument("--configs", type=int, nargs="+", default=None, help="default: 2 1")
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--repeats", type=int, default=3)
@@ -95,11 +174,12 @@ def main():
     a = ap.parse_args()
     out = Path(a.out)
     out.mkdir(parents=True, exist_ok=True)
-    for cfg in a.configs:
-        r = run(cfg, a.frames, a.calls, a.repeats)
+    for cfg in a.configs or ([1] if a.filters > 0 else [2, 1]):
+        r = run_bank(cfg, a.filters, a.frames, a.repeats) if a.filters > 0 else run(cfg, a.frames, a.calls, a.repeats)
         if a.commit:
             r["commit"] = a.commit
-        (out / f"config{cfg}.json").write_text(json.dumps(r, indent=1) + "\n")
+        name = f"bank{a.filters}_config{cfg}.json" if a.filters > 0 else f"config{cfg}.json"
+        (out / name).write_text(json.dumps(r, indent=1) + "\n")
         print(json.dumps(r), flush=True)
 
 
