@@ -129,6 +129,14 @@ template <int DI>
 constexpr int kNoSkip32x512 = (DI == 11 || DI == 12) ? kTileNoSkip : 0;
 template <int DI>
 constexpr int kDynNoSkip32x512 = DI <= 12 ? kTileNoSkip : 0;
+// The sum over the 16 lanes of a C/D row (lanes l ^ 1, 2, 4, 8 in that order), in every lane.
+__device__ __forceinline__ double sum16(double v) {
+  v += __shfl_xor(v, 1);
+  v += __shfl_xor(v, 2);
+  v += __shfl_xor(v, 4);
+  v += __shfl_xor(v, 8);
+  return v;
+}
 template <int I, int E, class F>
 __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (I < E) {
@@ -324,14 +332,20 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
   // (the float->int conversion is exact, ldexp underflows): its kernel value is exactly 0,
   // no masking per value.
   const double t_flush = prm.t_flush < 0.0 ? prm.t_flush : -__builtin_inf();   // (0: no flush)
-  auto gen_one = [&](int rb, int s) -> double {
-    const int r = g + NG * s;
-    const double* row = &RX[rb][r * RW];
+  // the exponent (times 64 / ln 2) of particle m against row g + NG s of the staged rows rb
+  auto gen_x = [&](int rb, int s) -> double {
+    const double* row = &RX[rb][(g + NG * s) * RW];
     double x = -(asq + row[DI]);
 #pragma unroll
     for (int j = 0; j < DI; ++j) x = fma(PLDS ? PA[m][j] : a2[j], row[j], x);
+    return x;
+  };
+  // the flush: a value whose exponent lies below tau's is exactly 0
+  auto flushed = [&](double x, double e) -> double { return x < t_flush ? 0.0 : e; };
+  auto gen_one = [&](int rb, int s) -> double {
+    const double x = gen_x(rb, s);
     const double e = exp2_64(x, tab);                      // padding rows: exactly 0
-    return x < t_flush ? 0.0 : e;                          // the flush: below tau, exactly 0
+    return flushed(x, e);
   };
   // this wave's activity word for the values it generated.  Lanes 16 q .. 16 q + 15 share a row
   // block and a training row, and lane groups q and q + NF share their bit (their rows lie in one
@@ -401,11 +415,12 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
   // before (kPlainStep: 32 x 512 with the coordinates in LDS, and d > 16), which branch as well.
   auto plain_step = [&](auto t0c, auto t1c, int ks, double (&bb)[BR * NTW]) {
     constexpr int T0 = decltype(t0c)::value, T1c = decltype(t1c)::value;
+    constexpr bool MUL = T0 < T1c;                           // (no tile: the tail's K-steps, generation only)
     const int buf = ks & (ASL - 1);
     double v[GV];
     double rr[RPT];
     unsigned mk = ~0u;                                       // this K-step's activity bits (SGPR)
-    if constexpr (SKIP) {
+    if constexpr (SKIP && MUL) {
       mk = 0;
 #pragma unroll
       for (int ww = 0; ww < NW; ++ww) mk |= Mk[buf][ww];
@@ -414,7 +429,7 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
     load_rows(ks + RA, rr);
     gen((ks + LOOK) & (RXS - 1), v);
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
+    for (int kk = 0; MUL && kk < 4; ++kk) {
       double af[MT];
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) af[mt] = As[buf][kk * 4 + lk][mt * 16 + li];
@@ -436,7 +451,8 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
   // front of the first branch, value by value in gen_one's arithmetic, each value stored to its
   // K* slot and its activity flags taken as soon as it exists (the slot is not read before the
   // next barrier); the word's store and the staged rows follow the last fragment.  This order
-  // measured fastest of those tried (profiles/obs_overlap/README.md).
+  // measured fastest of those tried (profiles/obs_overlap/README.md).  The activity read stands
+  // here and in plain_step: one definition of it changed K loops (profiles/tile_fold/README.md).
   auto full_step = [&](auto t0c, auto t1c, int ks, double (&bb)[BR * NTW]) {
     if constexpr (!SKIP || kPlainStep) {
       plain_step(t0c, t1c, ks, bb);
@@ -460,10 +476,7 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
       auto piece = [&](auto ic) {
         constexpr int i = decltype(ic)::value, s = i / 4;
         if constexpr (i % 4 == 0) {
-          const double* row = &RX[grb][(g + NG * s) * RW];
-          gx = -(asq + row[DI]);
-#pragma unroll
-          for (int j = 0; j < DI; ++j) gx = fma(PLDS ? PA[m][j] : a2[j], row[j], gx);
+          gx = gen_x(grb, s);
         } else if constexpr (i % 4 == 1) {
           gh = exp2_64_head(gx);
           gtj = tab[gh.ni & 63];
@@ -471,7 +484,7 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
           gp = exp2_64_poly(gh);
         } else {
           const double e = exp2_64_scale(gtj, gp, gh.ni);      // padding rows: exactly 0
-          const double vs = gx < t_flush ? 0.0 : e;            // the flush: below tau, exactly 0
+          const double vs = flushed(gx, e);
           As[gslot][g + NG * s][m] = vs;
           wd |= mask_bits(s, vs);
         }
@@ -542,15 +555,7 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
     }
   });
   // the rest of the block's K range (other waves' tiles): generate only
-  for (; ks < nks; ++ks) {
-    double v[GV];
-    double rr[RPT];
-    load_rows(ks + RA, rr);
-    gen((ks + LOOK) & (RXS - 1), v);
-    store((ks + LOOK) & (ASL - 1), v);
-    store_rows((ks + RA) & (RXS - 1), rr);
-    if (ks % SB == SB - 1) __syncthreads();
-  }
+  for (; ks < nks; ++ks) plain_step(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, ks, bb);
 
   if constexpr (DYN) {
     // Linear-kernel share: acc += X~ H for this block.  A fragment: lane l holds
@@ -664,11 +669,7 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
         for (int mt = 0; mt < MT; ++mt)
   #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            double v = ss[mt][r];
-            v += __shfl_xor(v, 1);
-            v += __shfl_xor(v, 2);
-            v += __shfl_xor(v, 4);
-            v += __shfl_xor(v, 8);
+            const double v = sum16(ss[mt][r]);
             if (li == 0) sred[w][mt * 16 + lk + 4 * r] = v;
           }
       }
@@ -693,11 +694,7 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
           double v = 0.0;
   #pragma unroll
           for (int nt = 0; nt < NTW; ++nt) v = fma(acc[mt][nt][r], acc[mt][nt][r], v);
-          v += __shfl_xor(v, 1);
-          v += __shfl_xor(v, 2);
-          v += __shfl_xor(v, 4);
-          v += __shfl_xor(v, 8);
-          qs[mt][r] = v;
+          qs[mt][r] = sum16(v);
         }
       if (li == 0) {
   #pragma unroll
@@ -816,11 +813,7 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
           for (int mt = 0; mt < MT; ++mt)
   #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              double v = ss[mt][r];
-              v += __shfl_xor(v, 1);
-              v += __shfl_xor(v, 2);
-              v += __shfl_xor(v, 4);
-              v += __shfl_xor(v, 8);
+              const double v = sum16(ss[mt][r]);
               if (li == 0) sred[h * NW + w][mt * 16 + lk + 4 * r] = v;
             }
         }
@@ -849,11 +842,7 @@ __global__ __launch_bounds__(64 * NW, (DI <= 16 ? 2 : 1)) void k_gp_tile(const T
             double v = 0.0;
   #pragma unroll
             for (int nt = h * NTH; nt < (h + 1) * NTH; ++nt) v = fma(acc[mt][nt][r], acc[mt][nt][r], v);
-            v += __shfl_xor(v, 1);
-            v += __shfl_xor(v, 2);
-            v += __shfl_xor(v, 4);
-            v += __shfl_xor(v, 8);
-            qs[mt][r] = v;
+            qs[mt][r] = sum16(v);
           }
         if (li == 0) {
   #pragma unroll
