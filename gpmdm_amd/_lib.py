@@ -72,6 +72,12 @@ class MarginalOut(ctypes.Structure):
 GPMDM_BACKSMOOTH_MAX_PAIRS = 1 << 36
 
 
+class MapOut(ctypes.Structure):
+    """gpmdm_map_out: host arrays, any may be NULL."""
+    _fields_ = [("index", _i64p), ("classes", _i64p), ("states", _dp), ("score", _dp), ("log_joint", _dp),
+                ("distinct", _i64p), ("delta", _dp), ("backpointer", _i64p)]
+
+
 class InnovationOut(ctypes.Structure):
     """gpmdm_innovation_out: host arrays, any may be NULL."""
     _fields_ = [("mean", _dp), ("spread", _dp), ("gp_variance", _dp), ("variance", _dp), ("residual", _dp),
@@ -150,6 +156,11 @@ _SIGS = {
     "gpmdm_backward_step": (c_int, [c_void_p, _dp, c_int64, _dp, _i64p, _dp, c_int64, _dp, _i64p, _dp, _dp, _dp,
                                     c_void_p]),
     "gpmdm_pf_smoothed_marginal": (c_int, [c_void_p, c_int, c_int, POINTER(MarginalOut), c_void_p]),
+    "gpmdm_pf_set_map": (c_int, [c_void_p, c_int]),
+    "gpmdm_pf_map_recording": (c_int, [c_void_p, POINTER(c_int)]),
+    "gpmdm_map_step": (c_int, [c_void_p, _dp, c_int64, _dp, _i64p, _dp, c_int64, _dp, _i64p, _dp, _dp, _i64p,
+                               c_void_p]),
+    "gpmdm_pf_map_path": (c_int, [c_void_p, c_int, POINTER(MapOut), c_void_p]),
     "gpmdm_pf_set_predictive": (c_int, [c_void_p, c_int]),
     "gpmdm_pf_innovation": (c_int, [c_void_p, POINTER(InnovationOut), c_void_p]),
     "gpmdm_pf_observation_gp": (c_int, [c_void_p, _dp, c_void_p]),

@@ -65,6 +65,7 @@ struct BsMomentArgs {
 
 struct BsGroupArgs {
   long long n;
+  const int* n_dev;               // the row count on the device (mappath.h's compacted slots), or nullptr: n
   int C;
   const int* cls;                 // n
   int* perm;                      // n      grouped position -> target

@@ -65,9 +65,10 @@ __global__ __launch_bounds__(kGroupB) void k_bs_group(BsGroupArgs a) {
   __shared__ int scan[2][kGroupB];
   __shared__ int base;
   const int t = threadIdx.x;
-  const long long len = (a.n + kGroupB - 1) / kGroupB;
-  const long long i0 = (long long)t * len < a.n ? (long long)t * len : a.n;
-  const long long i1 = i0 + len < a.n ? i0 + len : a.n;
+  const long long n = a.n_dev ? (long long)*a.n_dev : a.n;
+  const long long len = (n + kGroupB - 1) / kGroupB;
+  const long long i0 = (long long)t * len < n ? (long long)t * len : n;
+  const long long i1 = i0 + len < n ? i0 + len : n;
   if (t == 0) base = 0;
   __syncthreads();
   int blocks = 0;

@@ -144,6 +144,19 @@ struct BsScratch {
   DevBuf<int> perm, tab, hist, mult;
 };
 
+// One MAP step's device scratch (capi_mappath.hip mp_step): the sources' records, one class's
+// dynamics moments and tile partials, the targets' grouping and the ranges' maxima with their
+// source rows; and a decoded window's: the two slots' leaders (rows, lead; owner and rank while
+// they are elected), the compacted sources and targets, the scores by compact row (two halves),
+// the back-pointers by compact row, the compact sizes, and the scores and back-pointers of every
+// lag by particle
+struct MpScratch {
+  DevBuf<double> rec, mu, var, q, val;
+  DevBuf<int> idx, perm, tab;
+  DevBuf<double> Xs, Xt, llt, dc[2], delta;
+  DevBuf<int> owner, rank, rows[2], lead[2], cs, ct, psi_c, psi, count;
+};
+
 }  // namespace gpmdm::capi
 
 using namespace gpmdm;
@@ -418,6 +431,16 @@ struct gpmdm_pf {
   BsScratch bs;
   DevBuf<double> bs_w[2], bs_stage;
   Landing bs_out;
+  // MAP trajectory decoding over the same ring (gpmdm_pf_set_map, gpmdm_pf_map_path, mappath.h;
+  // capi_mappath.hip).  sm_map: every record also keeps the log-likelihood of the proposal each
+  // slot particle copies, ll[ridx[i]], in the plane sm_ll (sm_L + 1 frames; a cleared ring's root
+  // holds zeros) -- one more short launch per frame, none with the flag off.  The call's scratch
+  // is its own, grown on demand; mp_out: the path's rows and their pinned landing buffer (sm_wait
+  // covers it).
+  bool sm_map = false;
+  DevBuf<double> sm_ll;
+  MpScratch mp;
+  Landing mp_out;
   // Innovations and the GP's predictive variance (gpmdm_pf_set_predictive, gpmdm_pf_innovation,
   // gpmdm_pf_observation_gp and the banks'; obs_innov.h, capi_innov.hip).  predictive: every
   // weigh keeps vc = 1 - k^T K_y^-1 k of its particles in vc_prop (F x Pf, the order of X_prop
@@ -791,9 +814,9 @@ void launch_dyn_tiles(const gpmdm_model* m, const std::vector<GpImage>& dset, Ti
 int sm_set(gpmdm_pf* pf, int lag);     // (set_smoothing of a checked handle, single or bank)
 // gpmdm_predict_dyn's launches for class c over n device rows, q: predict_dyn_scratch doubles
 // (capi_model.hip)
-size_t predict_dyn_scratch(const gpmdm_model* m, int c, long long n);
+size_t predict_dyn_scratch(const gpmdm_model* m, int c, long long n, long long shape_n = -1);
 void launch_predict_dyn(const gpmdm_model* m, int c, const double* Xs, long long n, double* mu, double* var,
-                        double* q, hipStream_t s);
+                        double* q, hipStream_t s, long long shape_n = -1, const int* n_dev = nullptr);
 int iv_wait(gpmdm_pf* pf);             // an innovation call's launches in flight (capi_innov.hip)
 // gating (capi_gate.hip): the end of a gated-mode weigh on s; the log il2 table of the filter's
 // (new) model

@@ -5,6 +5,7 @@
 #include <memory>
 
 #include "capi_internal.h"
+#include "mappath.h"
 
 namespace gpmdm {
 thread_local std::string g_err;
@@ -163,13 +164,17 @@ static int finish_scratch(double* q, hipStream_t s) {
 // gpmdm_predict_dyn's launches (segment table, dynamics tiles, finish) for class c over the n
 // device rows Xs, with scratch q of predict_dyn_scratch doubles: one builder for the entry point
 // and the backward smoother's moments (capi_backsmooth.hip), so both give the same bits.
-size_t predict_dyn_scratch(const gpmdm_model* m, int c, long long n) {
-  return (size_t)m->dyn_set(n >= kWideRows)[c].n_parts() * (size_t)n + 4;
+// shape_n (>= 0): the image is the one a map over shape_n rows takes, whatever n is; n_dev: the
+// real row count lies on the device (<= n, which sizes the grids and the scratch) -- the MAP
+// decoder's compacted slots (capi_mappath.hip), whose rows must get the bits they get in a map
+// over the whole slot.
+size_t predict_dyn_scratch(const gpmdm_model* m, int c, long long n, long long shape_n) {
+  return (size_t)m->dyn_set((shape_n >= 0 ? shape_n : n) >= kWideRows)[c].n_parts() * (size_t)n + 4;
 }
 
 void launch_predict_dyn(const gpmdm_model* m, int c, const double* Xs, long long n, double* mu, double* var,
-                        double* q, hipStream_t s) {
-  const GpImage& g = m->dyn_set(n >= kWideRows)[c];
+                        double* q, hipStream_t s, long long shape_n, const int* n_dev) {
+  const GpImage& g = m->dyn_set((shape_n >= 0 ? shape_n : n) >= kWideRows)[c];
   const int nparts = g.n_parts();
   TileParams tp{};
   tp.seg[0] = g.seg();
@@ -178,7 +183,8 @@ void launch_predict_dyn(const gpmdm_model* m, int c, const double* Xs, long long
   tp.tiles_ub = g.tiles(n);
   tp.n_j_max = g.n_j;
   int* tab = reinterpret_cast<int*>(q + (size_t)nparts * n);   // segment table after q
-  launch_seg_table(tab, (int)n, g.tiles(n), s);
+  if (n_dev) launch_mp_seg_table(tab, n_dev, (int)n, g.geo.pt(), s);
+  else launch_seg_table(tab, (int)n, g.tiles(n), s);
   tp.seg_pos_begin = tab + 0;
   tp.seg_pos_end = tab + 1;
   tp.seg_out_base = tab + 2;

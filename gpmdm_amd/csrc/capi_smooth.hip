@@ -7,11 +7,13 @@
 // filter-major.  Kernels: smooth.h.
 #include "capi_internal.h"
 #include "smooth.h"
+#include "mappath.h"
 
 namespace gpmdm::capi {
 
-static size_t ring_bytes(long long P, int d, int L) {
-  return (size_t)(L + 1) * (size_t)P * (sizeof(double) * d + 2 * sizeof(int));
+// (map: the log-likelihood plane of gpmdm_pf_set_map is counted too)
+static size_t ring_bytes(long long P, int d, int L, bool map) {
+  return (size_t)(L + 1) * (size_t)P * (sizeof(double) * (d + (map ? 1 : 0)) + 2 * sizeof(int));
 }
 
 int sm_wait(gpmdm_pf* pf) {
@@ -20,11 +22,15 @@ int sm_wait(gpmdm_pf* pf) {
     pf->sm_pending = false;
   }
   TRY(pf->bs_out.wait());
+  TRY(pf->mp_out.wait());
   return pf->sm_out.wait();
 }
 
-static void launch_record(gpmdm_pf* pf, hipStream_t s) {
+// root: a cleared ring's root (no resample behind it: its log-likelihoods are zeros)
+static void launch_record(gpmdm_pf* pf, hipStream_t s, bool root = false) {
   const size_t k = (size_t)pf->sm_slot() * pf->P;
+  // (ll is final here: the resample's launches finished it, gpmdm_pf_resample)
+  if (pf->sm_map) launch_mp_ll_record(pf->ll, root ? nullptr : pf->ridx.p, pf->P, pf->sm_ll + k, s);
   SmRecordArgs a{};
   a.P = pf->P;
   a.d = pf->m->d;
@@ -57,7 +63,7 @@ int sm_clear(gpmdm_pf* pf, hipStream_t s) {
   pf->sm_depth = 0;
   pf->sm_root_anc = false;
   if (pf->sm_L == 0 || !pf->initialised) return GPMDM_OK;
-  launch_record(pf, s);
+  launch_record(pf, s, true);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(s));
   return GPMDM_OK;
@@ -68,8 +74,9 @@ int sm_set(gpmdm_pf* pf, int lag) {
   CHECK(lag >= 0 && lag <= GPMDM_SMOOTH_MAX_LAG, "lag must be in [0, GPMDM_SMOOTH_MAX_LAG]");
   if (pf->mid_step()) return fail(GPMDM_E_STATE, "set_smoothing between switch and resample");
   gpmdm_model* m = pf->m;
-  CHECK(lag == 0 || ring_bytes(pf->P, m->d, lag) <= kSmoothBytes,
-        "the history of this lag needs more than 1 GiB of device memory ((lag + 1) x P x (d + 1) doubles)");
+  CHECK(lag == 0 || ring_bytes(pf->P, m->d, lag, pf->sm_map) <= kSmoothBytes,
+        "the history of this lag needs more than 1 GiB of device memory ((lag + 1) x P x (d + 1) doubles; one more "
+        "per particle with map recording on)");
   HIPCHK(hipSetDevice(m->device));
   // a record or a read-out in flight, and the last frame's resample (it precedes the frame's
   // read-out; a pending pre-switch reads the cloud only, and stays pending)
@@ -79,12 +86,13 @@ int sm_set(gpmdm_pf* pf, int lag) {
     pf->sm_anc.release();
     pf->sm_cls.release();
     pf->sm_X.release();
+    pf->sm_ll.release();
   };
   drop_ring();
   pf->sm_L = pf->sm_depth = 0;
   if (lag == 0) return GPMDM_OK;
   const size_t n = (size_t)(lag + 1) * pf->P;
-  if (pf->sm_anc.alloc(n) || pf->sm_cls.alloc(n) || pf->sm_X.alloc(n * m->d)) {
+  if (pf->sm_anc.alloc(n) || pf->sm_cls.alloc(n) || pf->sm_X.alloc(n * m->d) || (pf->sm_map && pf->sm_ll.alloc(n))) {
     drop_ring();
     return GPMDM_E_NOMEM;
   }
@@ -217,6 +225,35 @@ int gpmdm_pf_set_smoothing(gpmdm_pf_t pf, int lag) {
 int gpmdm_bank_set_smoothing(gpmdm_pf_t pf, int lag) {
   CHECK(pf, "null handle");
   return sm_set(pf, lag);
+}
+
+int gpmdm_pf_set_map(gpmdm_pf_t pf, int on) {
+  CHECK(pf, "null handle");
+  CHECK(pf->F == 1, "map recording serves single filters, not banks");
+  CHECK(pf->n_ranks == 1, "map recording serves filters on one rank");
+  CHECK(!on || pf->sm_L > 0, "map recording needs smoothing on (gpmdm_pf_set_smoothing)");
+  if (pf->mid_step()) return fail(GPMDM_E_STATE, "set_map between switch and resample");
+  gpmdm_model* m = pf->m;
+  CHECK(!on || ring_bytes(pf->P, m->d, pf->sm_L, true) <= kSmoothBytes,
+        "the history with the log-likelihood plane needs more than 1 GiB of device memory ((lag + 1) x P x (d + 2) "
+        "doubles)");
+  HIPCHK(hipSetDevice(m->device));
+  TRY(sm_wait(pf));                    // (as sm_set: a record or a read-out in flight, the last frame)
+  HIPCHK(pf->zslot_free());
+  pf->sm_ll.release();
+  pf->sm_map = false;
+  if (!on) return GPMDM_OK;            // (the rest of the history stays)
+  if (pf->sm_ll.alloc((size_t)(pf->sm_L + 1) * pf->P)) return GPMDM_E_NOMEM;
+  pf->sm_map = true;
+  hipStream_t ls = life_stream(m->device);
+  CHECK(ls, "the library's lifecycle stream");
+  return sm_clear(pf, ls);
+}
+
+int gpmdm_pf_map_recording(gpmdm_pf_t pf, int* on) {
+  CHECK(pf, "null handle");
+  if (on) *on = pf->sm_map ? 1 : 0;
+  return GPMDM_OK;
 }
 
 int gpmdm_pf_smoothing_depth(gpmdm_pf_t pf, int* lag, int* depth) {

@@ -127,14 +127,28 @@ class MarginalSmoothed:
     weights: Optional[torch.Tensor] = None              # (n, P): of frame - lag's recorded cloud
 
 
-def backward_step(model, T, Xs, cs, Xt, ct, wt, a=None):
-    """One step of the marginal backward smoother (gpmdm_backward_step): sources ``Xs`` (n_s, d),
-    ``cs`` with filter weights ``a`` (None: 1 / n_s each), targets ``Xt`` (n_t, d), ``ct`` with
-    smoothing weights ``wt``, transition density f = T[c, c'] N(x'; mu_c'(x), v_c'(x)) with the
-    moments of ``model.map_x_dynamics_for_class``.  Returns ``(weights, log_den)`` as CPU tensors:
-    ``weights[i] = a_i sum_j wt_j f_ij / D_j`` and ``log_den[j] = log D_j``, ``D_j = sum_k a_k f_kj``
-    (-inf, and the target's mass lost, when no source reaches j).  A pure, bit-reproducible
-    function of its inputs."""
+@dataclass
+class MapPath:
+    """``GPMDM_PF.map_path``'s result; row l is lag ``lags[l]`` = l, i.e. frame ``frames[l]``.
+    ``indices[l]`` is the path's particle in frame ``frames[l]``'s recorded cloud (``export_state``'s
+    order), ``scores[l]`` its delta_l, ``log_joint`` = ``scores[0]``; ``distinct[l]`` the distinct
+    resampling ancestors of that cloud -- the rows the recursion ran on.  With ``log_joint`` = -inf
+    the unreachable rows hold index and class -1, NaN states and score -inf."""
+    lags: torch.Tensor                                  # (n,) int64
+    frames: torch.Tensor                                # (n,) int64: frame - lag
+    indices: torch.Tensor                               # (n,) int64
+    classes: torch.Tensor                               # (n,) int64
+    states: torch.Tensor                                # (n, d)
+    scores: torch.Tensor                                # (n,)
+    log_joint: float
+    distinct: torch.Tensor                              # (n,) int64
+    delta: Optional[torch.Tensor] = None                # (n, P)
+    backpointers: Optional[torch.Tensor] = None         # (n - 1, P) int64: into the next lag's cloud
+    observation_mean: Optional[torch.Tensor] = None     # (n, D)
+
+
+def _step_arrays(model, T, Xs, cs, Xt, ct, name):
+    """The arrays ``backward_step`` and ``map_step`` share, checked: (arr, T, Xs, cs, Xt, ct)."""
     d, C = int(model.d), int(model.n_classes)
 
     def arr(x, shape, what, dtype=np.float64):
@@ -152,15 +166,47 @@ def backward_step(model, T, Xs, cs, Xt, ct, wt, a=None):
     Xs_, Xt_ = arr(Xs, (None, d), "Xs"), arr(Xt, (None, d), "Xt")
     n_s, n_t = Xs_.shape[0], Xt_.shape[0]
     if n_s < 1 or n_t < 1:
-        raise ValueError("backward_step needs at least one source and one target")
+        raise ValueError(f"{name} needs at least one source and one target")
     cs_, ct_ = arr(cs, (n_s,), "cs", np.int64), arr(ct, (n_t,), "ct", np.int64)
-    wt_ = arr(wt, (n_t,), "wt")
-    a_ = None if a is None else arr(a, (n_s,), "a")
     for what, c in (("cs", cs_), ("ct", ct_)):
         if c.min() < 0 or c.max() >= C:
             raise ValueError(f"{what} must lie in [0, {C})")
     if n_s * n_t > _lib.GPMDM_BACKSMOOTH_MAX_PAIRS:
-        raise ValueError(f"backward_step serves up to 2^36 source-target pairs, got {n_s} x {n_t}")
+        raise ValueError(f"{name} serves up to 2^36 source-target pairs, got {n_s} x {n_t}")
+    return arr, Tm, Xs_, cs_, Xt_, ct_
+
+
+def map_step(model, T, Xs, cs, Xt, ct, delta=None, ll=None):
+    """One step of the MAP trajectory recursion (gpmdm_map_step): sources ``Xs`` (n_s, d), ``cs`` with
+    scores ``delta`` (None: zeros), targets ``Xt`` (n_t, d), ``ct`` with observation log-likelihoods
+    ``ll`` (None: zeros), transition density ``backward_step``'s f.  Returns ``(delta, backpointers)``
+    as CPU tensors: ``delta[j] = ll[j] + max_k [delta[k] + log f(k -> j)]`` and the lowest k attaining
+    it (-inf and -1 when no source reaches j or ``ll[j]`` is not finite).  Natural logarithms; the
+    rows are used as given (no de-duplication).  A pure, bit-reproducible function of its inputs."""
+    arr, Tm, Xs_, cs_, Xt_, ct_ = _step_arrays(model, T, Xs, cs, Xt, ct, "map_step")
+    n_s, n_t = Xs_.shape[0], Xt_.shape[0]
+    d_ = None if delta is None else arr(delta, (n_s,), "delta")
+    l_ = None if ll is None else arr(ll, (n_t,), "ll")
+    out, psi = np.zeros(n_t), np.zeros(n_t, dtype=np.int64)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(model.device).cuda_stream)
+    _lib.check(_lib.load().gpmdm_map_step(model.handle, _lib.dptr(Tm), n_s, _lib.dptr(Xs_), _lib.i64ptr(cs_),
+                                          _lib.dptr(d_), n_t, _lib.dptr(Xt_), _lib.i64ptr(ct_), _lib.dptr(l_),
+                                          _lib.dptr(out), _lib.i64ptr(psi), stream), "map_step")
+    return torch.from_numpy(out), torch.from_numpy(psi)
+
+
+def backward_step(model, T, Xs, cs, Xt, ct, wt, a=None):
+    """One step of the marginal backward smoother (gpmdm_backward_step): sources ``Xs`` (n_s, d),
+    ``cs`` with filter weights ``a`` (None: 1 / n_s each), targets ``Xt`` (n_t, d), ``ct`` with
+    smoothing weights ``wt``, transition density f = T[c, c'] N(x'; mu_c'(x), v_c'(x)) with the
+    moments of ``model.map_x_dynamics_for_class``.  Returns ``(weights, log_den)`` as CPU tensors:
+    ``weights[i] = a_i sum_j wt_j f_ij / D_j`` and ``log_den[j] = log D_j``, ``D_j = sum_k a_k f_kj``
+    (-inf, and the target's mass lost, when no source reaches j).  A pure, bit-reproducible
+    function of its inputs."""
+    arr, Tm, Xs_, cs_, Xt_, ct_ = _step_arrays(model, T, Xs, cs, Xt, ct, "backward_step")
+    n_s, n_t = Xs_.shape[0], Xt_.shape[0]
+    wt_ = arr(wt, (n_t,), "wt")
+    a_ = None if a is None else arr(a, (n_s,), "a")
     ws, ld = np.zeros(n_s), np.zeros(n_t)
     stream = ctypes.c_void_p(torch.cuda.current_stream(model.device).cuda_stream)
     _lib.check(_lib.load().gpmdm_backward_step(model.handle, _lib.dptr(Tm), n_s, _lib.dptr(Xs_), _lib.i64ptr(cs_),
@@ -369,8 +415,14 @@ class GPMDM_PF:
                  rng: str = "torch", seed=None, resample: str = "multinomial", process_group=None,
                  shard=None, exchange=None, dedup: bool = True, shard_order: bool = True,
                  dyn_tiles: str = "auto", devices=None, obs_cutoff: bool = False, transport: str = "rccl",
-                 smoothing_lag: int = 0, predictive: bool = False, gate=None, gate_limit: float = 0.5):
+                 smoothing_lag: int = 0, predictive: bool = False, gate=None, gate_limit: float = 0.5,
+                 map_path: bool = False):
         self._smoothing_lag = _check_smoothing_lag(smoothing_lag)
+        self._map_path = bool(map_path)
+        if self._map_path and not self._smoothing_lag:
+            raise ValueError("map_path=True needs smoothing_lag=L > 0 (the history it decodes)")
+        if self._map_path and (process_group is not None or shard is not None or devices is not None):
+            raise ValueError("map_path= serves single filters on one rank: no process_group, shard or devices")
         self._gate, self._gate_limit = _check_gate(gate, gate_limit)
         if self._gate is not None and (process_group is not None or shard is not None):
             raise ValueError("gate= serves single filters on one rank: no process_group or shard")
@@ -456,6 +508,12 @@ class GPMDM_PF:
                     _lib.check(lib.gpmdm_pf_set_smoothing(h, self._smoothing_lag), "smoothing_lag")
                 except Exception:
                     lib.gpmdm_pf_destroy(h)     # (a history above the memory limit: no handle is left behind)
+                    raise
+            if self._map_path:
+                try:
+                    _lib.check(lib.gpmdm_pf_set_map(h, 1), "map_path")
+                except Exception:
+                    lib.gpmdm_pf_destroy(h)
                     raise
             if self._predictive:
                 _lib.check(lib.gpmdm_pf_set_predictive(h, 1), "predictive")
@@ -967,6 +1025,26 @@ class GPMDM_PF:
     def smoothing_lag(self) -> int:
         return self._smoothing_lag
 
+    def set_map_path(self, on: bool = True):
+        """Record, with every frame of the history, the observation log-likelihood each recorded
+        particle was resampled with, for ``map_path`` (gpmdm_pf_set_map; the constructor's
+        ``map_path=True``): one more short launch per update and ``smoothing_lag`` + 1 rows of P
+        doubles.  Needs smoothing on; single filters on one rank; between updates only.  Turning it
+        on clears the history as ``set_smoothing`` does; a later ``set_smoothing`` keeps it."""
+        on = bool(on)
+        if on and not self._smoothing_lag:
+            raise ValueError("smoothing is off: build the filter with smoothing_lag=L or call set_smoothing(L)")
+        if self._peers or getattr(self, "_world", 1) > 1:
+            raise ValueError("map_path serves filters on one rank, not sharded filters")
+        self._sync_model()
+        _lib.check(_lib.load().gpmdm_pf_set_map(self._h, 1 if on else 0), "set_map_path")
+        self._map_path = on
+
+    @property
+    def map_recording(self) -> bool:
+        """Whether the history keeps what ``map_path`` needs (``map_path=True`` / ``set_map_path``)."""
+        return bool(getattr(self, "_map_path", False))
+
     @property
     def smoothing_depth(self) -> int:
         """min(smoothing lag, frames recorded since the history was last cleared): the largest
@@ -1040,6 +1118,59 @@ class GPMDM_PF:
         lags = np.arange(first, last + 1, dtype=np.int64)
         t = lambda x: None if x is None else torch.from_numpy(x)   # noqa: E731
         return MarginalSmoothed(t(lags), t(self.frame - lags), *map(t, (cp, sm, ms, es, ed, w)))
+
+    def map_path(self, lag=None, *, observation: bool = False, particles: bool = False) -> MapPath:
+        """The most probable class-and-state sequence over the last ``lag`` frames' recorded clouds
+        (None: the whole recorded depth), given what was seen in them: the MAP sequence estimate on
+        the particle grid, a Viterbi recursion with the filter's own proposal as transition density
+        (gpmdm_pf_map_path; Godsill, Doucet & West 2001).  With delta = 0 on the cloud ``lag`` frames
+        ago, each nearer frame's delta_l(j) = ll_l[j] + max_k [delta_{l+1}(k) + log f(k -> j)]
+        (``map_step``; ll_l[j] the log-likelihood particle j was resampled with), the path ends in
+        the lowest-index argmax of delta_0 and follows the back-pointers.  Where per-frame argmaxes
+        of ``smoothed`` / ``smoothed_marginal`` may switch class along transitions ``T`` forbids,
+        this is one trajectory that the model supports.  ``observation``: ``model.map_x_to_y`` of the
+        path's states; ``particles``: delta and the back-pointers of every recorded particle.
+
+        Ties go to the lowest index, no draw is taken and nothing in the filter changes: later
+        updates are bitwise those without the call, and the same history gives the same bits.  The
+        recursion runs on each frame's distinct resampling ancestors (``distinct``), so far lags
+        cost little.  Needs ``smoothing_lag`` and ``map_path=True`` / ``set_map_path``; single
+        filters on one rank, up to 262144 particles."""
+        if lag is not None and (isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or
+                                not 1 <= int(lag) <= _lib.GPMDM_SMOOTH_MAX_LAG):
+            raise ValueError(f"lag must be None or an integer in [1, {_lib.GPMDM_SMOOTH_MAX_LAG}], got {lag!r}")
+        if self._peers or getattr(self, "_world", 1) > 1:
+            raise ValueError("map_path serves filters on one rank, not sharded filters")
+        P = self._num_particles
+        if P * P > _lib.GPMDM_BACKSMOOTH_MAX_PAIRS:
+            raise ValueError(f"map_path serves up to 262144 particles (2^36 pairs per step), got {P}")
+        if not self._smoothing_lag:
+            raise ValueError("smoothing is off: build the filter with smoothing_lag=L or call set_smoothing(L)")
+        if not getattr(self, "_map_path", False):
+            raise ValueError("map recording is off: build the filter with map_path=True or call set_map_path()")
+        depth = self.smoothing_depth
+        n_lag = depth if lag is None else int(lag)
+        if n_lag > depth or n_lag < 1:
+            raise ValueError(f"lag {n_lag} is outside [1, the recorded depth {depth}] (smoothing lag {self._smoothing_lag})")
+        d, n = self.latent_dim, n_lag + 1
+        ix, cl, ds = (np.zeros(n, dtype=np.int64) for _ in range(3))
+        st, sc, lj = np.zeros((n, d)), np.zeros(n), np.zeros(1)
+        de = np.zeros((n, P)) if particles else None
+        bp = np.zeros((n_lag, P), dtype=np.int64) if particles else None
+        out = _lib.MapOut(_lib.i64ptr(ix), _lib.i64ptr(cl), _lib.dptr(st), _lib.dptr(sc), _lib.dptr(lj),
+                          _lib.i64ptr(ds), _lib.dptr(de), _lib.i64ptr(bp))
+        _lib.check(_lib.load().gpmdm_pf_map_path(self._h, n_lag, ctypes.byref(out), self._stream()), "map_path")
+        lags = np.arange(n, dtype=np.int64)
+        t = lambda x: None if x is None else torch.from_numpy(x)   # noqa: E731
+        om = None
+        if observation:
+            ok = np.isfinite(st).all(axis=1)
+            om = torch.full((n, self.observation_dim), float("nan"), dtype=torch.float64)
+            if ok.any():
+                y = self._gpmdm.map_x_to_y(torch.from_numpy(st[ok]))
+                y = y[0] if isinstance(y, (tuple, list)) else y
+                om[torch.from_numpy(ok)] = y.detach().cpu().to(torch.float64)
+        return MapPath(t(lags), t(self.frame - lags), t(ix), t(cl), t(st), t(sc), float(lj[0]), t(ds), t(de), t(bp), om)
 
     @property
     def frame(self) -> int:

@@ -850,6 +850,67 @@ int gpmdm_backward_step(gpmdm_model_t model, const double* T, int64_t n_s, const
 int gpmdm_pf_smoothed_marginal(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_marginal_out* out,
                                void* stream);
 
+/* MAP trajectory decoding over the history ring: the most probable class-and-state sequence on
+ * the particle grid (particle Viterbi; Godsill, Doucet & West 2001) -- one consistent trajectory
+ * where gpmdm_pf_smoothed and gpmdm_pf_smoothed_marginal give per-frame marginals.  It takes no
+ * draw.  Let frame t be the last completed resample and slot l the ring's record of frame t - l:
+ * X_l[i], c_l[i], a_l[i].  gpmdm_pf_set_map(pf, 1) adds a plane l_l[i] to the ring: the
+ * log-likelihood of the proposal that slot particle i copies, gpmdm_pf_export's ll[resample_idx[i]]
+ * of that frame -- the value the frame's normaliser read, masked and gated as the frame was.
+ * log f(k -> j) is gpmdm_backward_step's transition density with source (X_{l+1}[k], c_{l+1}[k])
+ * and target (X_l[j], c_l[j]).  For a window of n lags, 1 <= n <= depth:
+ *   delta_n(k) = 0   (the root cloud is flat over its support; its l is never read: a cleared
+ *                     ring's root has none),
+ *   delta_l(j) = l_l[j] + max_k [delta_{l+1}(k) + log f(k -> j)]       for l = n - 1 .. 0,
+ *   psi_l(j)   = the lowest k attaining the maximum; psi_l(j) = -1 and delta_l(j) = -inf when no
+ *                source reaches j or l_l[j] is not finite; a NaN candidate never wins,
+ *   j*_0 = the lowest index attaining max_j delta_0(j),  j*_{l+1} = psi_l(j*_l),
+ *   log_joint = delta_0(j*_0).
+ * If log_joint is -inf the call succeeds with index and classes -1, states NaN and score -inf from
+ * the first unreachable lag on.  All values are natural logarithms.  There are no floating-point
+ * atomics, ties go to the lowest index always, and the same inputs give the same bits.
+ * Copies of a resampled particle are bitwise-equal candidates and a maximum has no order: the
+ * recursion runs on each slot's leaders (per distinct resampling ancestor the copy of lowest
+ * index, in increasing index) and gives the delta and psi of the recursion over all P rows.
+ * gpmdm_pf_set_map(pf, on): needs smoothing on (gpmdm_pf_set_smoothing), between frames only
+ * (GPMDM_E_STATE inside one), single filters on one rank; allocates the plane, (lag + 1) x P
+ * doubles -- counted in the history's 1 GiB limit while the flag is on -- and clears the history
+ * exactly as gpmdm_pf_set_smoothing does (a cleared ring's root records l = 0).  A later
+ * gpmdm_pf_set_smoothing keeps the flag and resizes the plane.  With the flag on every resample
+ * issues one more short launch (l_dst[i] = ll[ridx[i]]); with it off a frame issues exactly the
+ * launches it issued before.  on = 0 releases the plane and keeps the rest of the history.
+ * gpmdm_pf_map_recording: the flag.
+ * gpmdm_map_step (host arrays; a pure function of its inputs; no de-duplication, the caller's rows
+ * are used as given): sources Xs (n_s x d), cs with scores delta_s (NULL: zeros), targets Xt
+ * (n_t x d), ct with log-likelihoods ll_t (NULL: zeros);
+ *   delta_out[j] = ll_t[j] + max_k [delta_s[k] + log f(k -> j)],   psi_out[j] = the lowest such k
+ * (-inf and -1 as above).  Refusals are gpmdm_backward_step's: sizes, more than 2^36 pairs, more
+ * than 1 GiB of records, a class outside [0, C).  delta_out and psi_out may be NULL.
+ * gpmdm_pf_map_path(pf, lag, out, stream): the window of `lag` lags behind the last completed
+ * frame; row l of each output that is not NULL is lag l, frame t - l.  The rules are
+ * gpmdm_pf_smoothed_marginal's: GPMDM_E_INVALID, decided before any launch, for banks, sharded
+ * filters, smoothing or map recording off, lag outside [1, depth], more than 2^36 pairs per step,
+ * more than 1 GiB of staging (delta and psi of every lag by particle, and the records);
+ * GPMDM_E_STATE between a switch and its resample.  The live filter is untouched (no draw, no
+ * frame or health counter, a pending pre-switch stays pending, later frames are bitwise those
+ * without the call); everything is queued on `stream` and ends with one copy-out and one wait. */
+typedef struct gpmdm_map_out {   /* host arrays; any may be NULL; n = lag + 1 */
+  int64_t* index;         /* n: j*_l, the path's particle in slot l */
+  int64_t* classes;       /* n */
+  double* states;         /* n x d */
+  double* score;          /* n: delta_l(j*_l) */
+  double* log_joint;      /* 1 */
+  int64_t* distinct;      /* n: the slots' leaders (distinct resampling ancestors; P for a cleared ring's root) */
+  double* delta;          /* n x P: delta_l per particle of slot l */
+  int64_t* backpointer;   /* lag x P: psi_l per particle of slot l, an index into slot l + 1 */
+} gpmdm_map_out;
+int gpmdm_pf_set_map(gpmdm_pf_t pf, int on);
+int gpmdm_pf_map_recording(gpmdm_pf_t pf, int* on);
+int gpmdm_map_step(gpmdm_model_t model, const double* T, int64_t n_s, const double* Xs, const int64_t* cs,
+                   const double* delta_s, int64_t n_t, const double* Xt, const int64_t* ct, const double* ll_t,
+                   double* delta_out, int64_t* psi_out, void* stream);
+int gpmdm_pf_map_path(gpmdm_pf_t pf, int lag, const gpmdm_map_out* out, void* stream);
+
 /* Message of the last failed call on this thread ("" if none). */
 const char* gpmdm_last_error(void);
 
