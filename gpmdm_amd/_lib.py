@@ -78,6 +78,15 @@ class MapOut(ctypes.Structure):
                 ("distinct", _i64p), ("delta", _dp), ("backpointer", _i64p)]
 
 
+GPMDM_BACKSAMPLE_RANGE = 1024
+
+
+class SampleOut(ctypes.Structure):
+    """gpmdm_sample_out: host arrays, any may be NULL."""
+    _fields_ = [("index", _i64p), ("classes", _i64p), ("states", _dp), ("class_prob", _dp), ("state_mean", _dp),
+                ("alive", _i64p), ("distinct", _i64p), ("obs_mean", _dp), ("obs_spread", _dp)]
+
+
 class InnovationOut(ctypes.Structure):
     """gpmdm_innovation_out: host arrays, any may be NULL."""
     _fields_ = [("mean", _dp), ("spread", _dp), ("gp_variance", _dp), ("variance", _dp), ("residual", _dp),
@@ -161,6 +170,10 @@ _SIGS = {
     "gpmdm_map_step": (c_int, [c_void_p, _dp, c_int64, _dp, _i64p, _dp, c_int64, _dp, _i64p, _dp, _dp, _i64p,
                                c_void_p]),
     "gpmdm_pf_map_path": (c_int, [c_void_p, c_int, POINTER(MapOut), c_void_p]),
+    "gpmdm_backward_sample_step": (c_int, [c_void_p, _dp, c_int64, _dp, _i64p, _dp, c_int64, _dp, _i64p, _dp, _i64p, _dp,
+                                           c_void_p]),
+    "gpmdm_pf_sample_trajectories": (c_int, [c_void_p, c_int64, c_int, POINTER(c_uint64), POINTER(SampleOut),
+                                             c_void_p]),
     "gpmdm_pf_set_predictive": (c_int, [c_void_p, c_int]),
     "gpmdm_pf_innovation": (c_int, [c_void_p, POINTER(InnovationOut), c_void_p]),
     "gpmdm_pf_observation_gp": (c_int, [c_void_p, _dp, c_void_p]),

@@ -26,11 +26,11 @@ SOURCES = ["gp_tile.hip", "gp_tile_d1.hip", "gp_tile_d2.hip", "gp_tile_d3.hip", 
            "obs_cutoff.hip", "obs_cutoff_d9.hip", "memory.hip", "cutoff_image.hip", "obs_readout.hip",
            "forecast.hip", "capi_forecast.hip", "smooth.hip", "capi_smooth.hip", "obs_innov.hip",
            "capi_innov.hip", "obs_gate.hip", "capi_gate.hip", "backsmooth.hip", "capi_backsmooth.hip",
-           "mappath.hip", "capi_mappath.hip"]
+           "mappath.hip", "capi_mappath.hip", "backsample.hip", "capi_backsample.hip"]
 HEADERS = [CSRC / "common.h", CSRC / "geometry.h", CSRC / "host_image.h", CSRC / "gp_tile.h", CSRC / "pf_kernels.h",
            CSRC / "status.h", CSRC / "capi_internal.h", CSRC / "obs_cutoff.h", CSRC / "obs_readout.h",
            CSRC / "forecast.h", CSRC / "smooth.h", CSRC / "obs_readout_tile.h", CSRC / "obs_innov.h", CSRC / "obs_gate.h",
-           CSRC / "backsmooth.h", CSRC / "mappath.h",
+           CSRC / "backsmooth.h", CSRC / "mappath.h", CSRC / "backsample.h",
            ROOT / "include" / "gpmdm_hip.h"]
 ARCH = "gfx950"
 

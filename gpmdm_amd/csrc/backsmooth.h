@@ -110,6 +110,97 @@ struct BsReduceArgs {
   double* out;                    // {class mass[C], mean state[d], mass, ess, ess_distinct}
 };
 
+#ifdef __HIPCC__
+// ---------------------------------------------------------------------------------
+// Device code the denominator pass shares with backward simulation (backsample.h): one
+// definition of the running sums, of a pair's exponent and of a range's loop.
+constexpr double kHalfLog2e = 0.72134752044448170368;   // 1/2 log2 e
+constexpr double kLn2 = 0.69314718055994530942;
+
+// Running sums s 2^m, m an integer (or -inf with s = 0).
+__device__ __forceinline__ int bs_shift(double from, double to) {   // from - to <= 0, clamped (2^-4096 = 0)
+  return (int)fmax(from - to, -4096.0);
+}
+__device__ __forceinline__ void bs_add(double& m, double& s, double l) {
+  if (!(l > -INFINITY)) return;          // a term of weight zero
+  if (l > m) {
+    const double mn = ceil(l);
+    s = ldexp(s, bs_shift(m, mn));       // exact (m = -inf: s = 0)
+    m = mn;
+  }
+  s += exp2(l - m);
+}
+__device__ __forceinline__ void bs_merge(double& m, double& s, double m2, double s2) {
+  if (!(s2 > 0.0)) return;
+  if (m2 > m) {
+    s = ldexp(s, bs_shift(m, m2)) + s2;
+    m = m2;
+  } else {
+    s += ldexp(s2, bs_shift(m2, m));
+  }
+}
+
+__device__ __forceinline__ int bs_class(int c, int C) { return c < 0 ? 0 : (c >= C ? C - 1 : c); }
+
+// Block b of a pass over the grouped targets (k_bs_group's block starts): its class, false past
+// the last block; and thread tid's grouped position in it.
+__device__ __forceinline__ bool bs_block_class(const int* tab, int C, int b, int& c) {
+  const int* bstart = tab + C + 1;
+  if (b >= bstart[C]) return false;
+  c = 0;
+  while (c + 1 < C && b >= bstart[c + 1]) ++c;
+  return true;
+}
+__device__ __forceinline__ long long bs_block_pos(const int* tab, int C, int b, int c, int tid) {
+  return (long long)tab[c] + (long long)(b - tab[C + 1 + c]) * kBsB + tid;
+}
+template <int D>
+__device__ __forceinline__ void bs_load_target(const double* Xt, const int* perm, long long pos, bool live, double (&x)[D]) {
+  const long long j = live ? perm[pos] : 0;
+#pragma unroll
+  for (int q = 0; q < D; ++q) x[q] = live ? Xt[j * D + q] : 0.0;
+}
+
+// log2 of a_k f_kj: target x against the source record row = {mu[D], 1/v[D], g}
+template <int D>
+__device__ __forceinline__ double bs_pair_exponent(const double (&x)[D], const double* row) {
+  double qd = 0.0;
+#pragma unroll
+  for (int q = 0; q < D; ++q) {
+    const double df = x[q] - row[q];
+    qd = fma(df, df * row[D + q], qd);
+  }
+  return fma(qd, -kHalfLog2e, row[2 * D]);
+}
+
+// Sources [k0, k1) of one class's records through LDS, kBsTile at a time (every lane reads the
+// same address: a broadcast), added to the thread's running sum in index order.  after(k, l, m, s)
+// sees the sum behind source k, whose exponent was l; returning true ends the thread's part (it
+// keeps the barriers).  Called by every thread of the block.
+template <int D, class After>
+__device__ __forceinline__ void bs_den_range(const double* rec, long long k0, long long k1, bool live,
+                                             const double (&x)[D], double* tile, double& m, double& s, After after) {
+  constexpr int R = 2 * D + 1;
+  const int tid = threadIdx.x;
+  for (long long kt = k0; kt < k1; kt += kBsTile) {
+    const int rows = (int)(k1 - kt < kBsTile ? k1 - kt : kBsTile);
+    for (int e = tid; e < rows * R; e += kBsB) tile[e] = rec[kt * R + e];
+    __syncthreads();
+    if (live) {
+      for (int r = 0; r < rows; ++r) {
+        const double l = bs_pair_exponent<D>(x, tile + r * R);
+        bs_add(m, s, l);
+        if (after(kt + r, l, m, s)) {
+          live = false;
+          break;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+#endif  // __HIPCC__
+
 void launch_bs_moments(const BsMomentArgs& a, hipStream_t s);
 void launch_bs_group(const BsGroupArgs& a, hipStream_t s);
 void launch_bs_den(const BsPassArgs& a, hipStream_t s);

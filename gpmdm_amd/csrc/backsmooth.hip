@@ -3,36 +3,8 @@
 
 namespace gpmdm {
 
-constexpr double kHalfLog2e = 0.72134752044448170368;   // 1/2 log2 e
 constexpr double kLog2TwoPi = 2.6514961294723187980;    // log2 (2 pi)
-constexpr double kLn2 = 0.69314718055994530942;
 constexpr int kGroupB = 1024;
-
-// ---------------------------------------------------------------------------------
-// Running sums s 2^m, m an integer (or -inf with s = 0).
-__device__ __forceinline__ int bs_shift(double from, double to) {   // from - to <= 0, clamped (2^-4096 = 0)
-  return (int)fmax(from - to, -4096.0);
-}
-__device__ __forceinline__ void bs_add(double& m, double& s, double l) {
-  if (!(l > -INFINITY)) return;          // a term of weight zero
-  if (l > m) {
-    const double mn = ceil(l);
-    s = ldexp(s, bs_shift(m, mn));       // exact (m = -inf: s = 0)
-    m = mn;
-  }
-  s += exp2(l - m);
-}
-__device__ __forceinline__ void bs_merge(double& m, double& s, double m2, double s2) {
-  if (!(s2 > 0.0)) return;
-  if (m2 > m) {
-    s = ldexp(s, bs_shift(m, m2)) + s2;
-    m = m2;
-  } else {
-    s += ldexp(s2, bs_shift(m2, m));
-  }
-}
-
-__device__ __forceinline__ int bs_class(int c, int C) { return c < 0 ? 0 : (c >= C ? C - 1 : c); }
 
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBsB) void k_bs_moments(BsMomentArgs a) {
@@ -109,45 +81,19 @@ __global__ __launch_bounds__(kGroupB) void k_bs_group(BsGroupArgs a) {
 // k_bs_group); range blockIdx.y of the sources goes through LDS 64 records of class c at a time.
 template <int D>
 __global__ __launch_bounds__(kBsB) void k_bs_den(BsPassArgs a) {
-  constexpr int R = 2 * D + 1;
-  __shared__ double tile[kBsTile * R];
-  const int tid = threadIdx.x, C = a.C;
-  const int b = blockIdx.x;
-  const int* bstart = a.tab + C + 1;
-  if (b >= bstart[C]) return;            // (uniform over the block)
-  int c = 0;
-  while (c + 1 < C && b >= bstart[c + 1]) ++c;
-  const long long pos = (long long)a.tab[c] + (long long)(b - bstart[c]) * kBsB + tid;
-  const bool live = pos < a.tab[c + 1];
+  __shared__ double tile[kBsTile * (2 * D + 1)];
+  int c;
+  if (!bs_block_class(a.tab, a.C, blockIdx.x, c)) return;   // (uniform over the block)
+  const long long pos = bs_block_pos(a.tab, a.C, blockIdx.x, c, threadIdx.x);
+  bool live = pos < a.tab[c + 1];
   double x[D];
-  {
-    const long long j = live ? a.perm[pos] : 0;
-#pragma unroll
-    for (int q = 0; q < D; ++q) x[q] = live ? a.Xt[j * D + q] : 0.0;
-  }
+  bs_load_target<D>(a.Xt, a.perm, pos, live, x);
   const long long len = (a.n_s + a.split - 1) / a.split;
   const long long k0 = (long long)blockIdx.y * len;
   const long long k1 = k0 + len < a.n_s ? k0 + len : a.n_s;
-  const double* rec = a.rec + (long long)c * a.n_s * R;
   double m = -INFINITY, s = 0.0;
-  for (long long kt = k0; kt < k1; kt += kBsTile) {
-    const int rows = (int)(k1 - kt < kBsTile ? k1 - kt : kBsTile);
-    for (int e = tid; e < rows * R; e += kBsB) tile[e] = rec[kt * R + e];
-    __syncthreads();
-    if (live) {
-      for (int r = 0; r < rows; ++r) {
-        const double* row = tile + r * R;
-        double qd = 0.0;
-#pragma unroll
-        for (int q = 0; q < D; ++q) {
-          const double df = x[q] - row[q];
-          qd = fma(df, df * row[D + q], qd);
-        }
-        bs_add(m, s, fma(qd, -kHalfLog2e, row[2 * D]));
-      }
-    }
-    __syncthreads();
-  }
+  bs_den_range<D>(a.rec + (long long)c * a.n_s * (2 * D + 1), k0, k1, live, x, tile, m, s,
+                  [](long long, double, double, double) { return false; });
   if (live) {
     double* out = a.part + (long long)blockIdx.y * a.n_t + pos;    // the m plane, then the s plane
     out[0] = m;

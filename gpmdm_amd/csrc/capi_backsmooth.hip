@@ -10,16 +10,45 @@ namespace gpmdm::capi {
 
 constexpr long long kBsMaxPairs = 1ll << 36;
 
-static size_t bs_record_bytes(int C, int d, long long n_s) {
+size_t bs_record_bytes(int C, int d, long long n_s) {
   return sizeof(double) * (size_t)C * (size_t)n_s * (size_t)(2 * d + 1);
 }
 
 // The step's refusals, decided before any launch.
-static int bs_check(const gpmdm_model* m, long long n_s, long long n_t) {
+int bs_check(const gpmdm_model* m, long long n_s, long long n_t) {
   CHECK(n_s >= 1 && n_t >= 1 && n_s < (1ll << 31) && n_t < (1ll << 31), "backward step: n_s and n_t must be in [1, 2^31)");
   CHECK(n_s <= kBsMaxPairs / n_t, "backward step: more than 2^36 source-target pairs (P > 262144)");
   CHECK(bs_record_bytes(m->C, m->d, n_s) <= kSmoothBytes,
         "backward step: the sources' moments need more than 1 GiB of device staging (C x n_s x (2 d + 1) doubles)");
+  return GPMDM_OK;
+}
+
+// The sources' records of every class (k_bs_moments behind gpmdm_predict_dyn's launches), queued
+// on s; the buffers are grown as needed.
+int bs_records(const gpmdm_model* m, DevBuf<double>& rec, DevBuf<double>& mu, DevBuf<double>& var, DevBuf<double>& q,
+               const double* T, long long n_s, const double* Xs, const int* cs, const double* a, hipStream_t s) {
+  const int C = m->C, d = m->d;
+  size_t nq = 0;
+  for (int c = 0; c < C; ++c) nq = std::max(nq, predict_dyn_scratch(m, c, n_s));
+  TRY(rec.grow((size_t)C * n_s * (2 * d + 1), s));
+  TRY(mu.grow((size_t)n_s * d, s));
+  TRY(var.grow((size_t)n_s * d, s));
+  TRY(q.grow(nq, s));
+  for (int c = 0; c < C; ++c) {
+    launch_predict_dyn(m, c, Xs, n_s, mu, var, q, s);
+    BsMomentArgs ma{};
+    ma.n = n_s;
+    ma.C = C;
+    ma.d = d;
+    ma.c = c;
+    ma.mu = mu;
+    ma.var = var;
+    ma.cls = cs;
+    ma.a = a;
+    ma.T = T;
+    ma.rec = rec;
+    launch_bs_moments(ma, s);
+  }
   return GPMDM_OK;
 }
 
@@ -30,31 +59,11 @@ static int bs_step(const gpmdm_model* m, BsScratch& sc, const double* T, long lo
                    double* ws, double* log_den, hipStream_t s) {
   const int C = m->C, d = m->d;
   const int split_d = bs_split(n_t, n_s), split_w = bs_split(n_s, n_t);
-  size_t nq = 0;
-  for (int c = 0; c < C; ++c) nq = std::max(nq, predict_dyn_scratch(m, c, n_s));
-  TRY(sc.rec.grow((size_t)C * n_s * (2 * d + 1), s));
-  TRY(sc.mu.grow((size_t)n_s * d, s));
-  TRY(sc.var.grow((size_t)n_s * d, s));
-  TRY(sc.q.grow(nq, s));
+  TRY(bs_records(m, sc.rec, sc.mu, sc.var, sc.q, T, n_s, Xs, cs, a, s));
   TRY(sc.perm.grow((size_t)n_t, s));
   TRY(sc.tab.grow((size_t)2 * kMaxClasses + 2, s));
   TRY(sc.lw.grow((size_t)n_t, s));
   TRY(sc.part.grow(2 * std::max((size_t)split_d * n_t, (size_t)split_w * n_s), s));
-  for (int c = 0; c < C; ++c) {
-    launch_predict_dyn(m, c, Xs, n_s, sc.mu, sc.var, sc.q, s);
-    BsMomentArgs ma{};
-    ma.n = n_s;
-    ma.C = C;
-    ma.d = d;
-    ma.c = c;
-    ma.mu = sc.mu;
-    ma.var = sc.var;
-    ma.cls = cs;
-    ma.a = a;
-    ma.T = T;
-    ma.rec = sc.rec;
-    launch_bs_moments(ma, s);
-  }
   BsGroupArgs ga{};
   ga.n = n_t;
   ga.C = C;
@@ -96,7 +105,7 @@ static int bs_step(const gpmdm_model* m, BsScratch& sc, const double* T, long lo
   return GPMDM_OK;
 }
 
-static int to_classes(const int64_t* src, long long n, int C, std::vector<int>& dst, const char* what) {
+int bs_to_classes(const int64_t* src, long long n, int C, std::vector<int>& dst, const char* what) {
   dst.resize((size_t)n);
   for (long long i = 0; i < n; ++i) {
     CHECK(src[i] >= 0 && src[i] < C, std::string("backward step: a class of the ") + what + " is outside [0, C)");
@@ -117,8 +126,8 @@ int gpmdm_backward_step(gpmdm_model_t m, const double* T, int64_t n_s, const dou
   TRY(bs_check(m, n_s, n_t));
   const int C = m->C, d = m->d;
   std::vector<int> cs32, ct32;
-  TRY(to_classes(cs, n_s, C, cs32, "sources"));
-  TRY(to_classes(ct, n_t, C, ct32, "targets"));
+  TRY(bs_to_classes(cs, n_s, C, cs32, "sources"));
+  TRY(bs_to_classes(ct, n_t, C, ct32, "targets"));
   HIPCHK(hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
   // the call's own buffers and scratch, released when it has waited for its launches

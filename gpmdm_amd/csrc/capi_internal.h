@@ -20,6 +20,8 @@
 //                      gpmdm_bank_smoothed)
 //   capi_backsmooth.hip  marginal backward smoothing over that ring (gpmdm_backward_step,
 //                      gpmdm_pf_smoothed_marginal)
+//   capi_backsample.hip  backward simulation over that ring (gpmdm_backward_sample_step,
+//                      gpmdm_pf_sample_trajectories)
 //   capi_innov.hip     per-joint innovations and the GP's predictive variance (gpmdm_pf_set_predictive,
 //                      gpmdm_pf_innovation, gpmdm_pf_observation_gp and the banks')
 //   capi_gate.hip      outlier gating inside the frame (gpmdm_pf_set_gate, gpmdm_pf_gate_report)
@@ -155,6 +157,18 @@ struct MpScratch {
   DevBuf<int> idx, perm, tab;
   DevBuf<double> Xs, Xt, llt, dc[2], delta;
   DevBuf<int> owner, rank, rows[2], lead[2], cs, ct, psi_c, psi, count;
+};
+
+// One backward-simulation step's device scratch (capi_backsample.hip fs_moments / fs_targets): the
+// sources' records, one class's dynamics moments and tile partials, a chunk of targets' grouping,
+// the ranges' partial sums and what k_fs_pick leaves per target; and a sampled window's: the
+// uniforms, the result rows {index, class, state} of every lag, the distinct count's marks, and
+// for the pose of a lag with dead trajectories the alive rows' flags, grouping and states
+struct FsScratch {
+  DevBuf<double> rec, mu, var, q, part, res, scale;
+  DevBuf<int> perm, tab, range;
+  DevBuf<double> u, X, ro_part, ro_X;
+  DevBuf<int> idx, cls, mark, ro_flag, ro_perm, ro_tab;
 };
 
 }  // namespace gpmdm::capi
@@ -441,6 +455,11 @@ struct gpmdm_pf {
   DevBuf<double> sm_ll;
   MpScratch mp;
   Landing mp_out;
+  // Backward simulation over the same ring (gpmdm_pf_sample_trajectories, backsample.h;
+  // capi_backsample.hip): scratch of its own, grown on demand, and the per-lag rows and poses with
+  // their pinned landing buffer (sm_wait covers fs_out).
+  FsScratch fs;
+  Landing fs_out;
   // Innovations and the GP's predictive variance (gpmdm_pf_set_predictive, gpmdm_pf_innovation,
   // gpmdm_pf_observation_gp and the banks'; obs_innov.h, capi_innov.hip).  predictive: every
   // weigh keeps vc = 1 - k^T K_y^-1 k of its particles in vc_prop (F x Pf, the order of X_prop
@@ -817,6 +836,13 @@ int sm_set(gpmdm_pf* pf, int lag);     // (set_smoothing of a checked handle, si
 size_t predict_dyn_scratch(const gpmdm_model* m, int c, long long n, long long shape_n = -1);
 void launch_predict_dyn(const gpmdm_model* m, int c, const double* Xs, long long n, double* mu, double* var,
                         double* q, hipStream_t s, long long shape_n = -1, const int* n_dev = nullptr);
+// the backward step's parts that backward simulation shares (capi_backsmooth.hip): the refusals
+// decided before any launch, the classes as the kernels take them, and the sources' records
+size_t bs_record_bytes(int C, int d, long long n_s);
+int bs_check(const gpmdm_model* m, long long n_s, long long n_t);
+int bs_to_classes(const int64_t* src, long long n, int C, std::vector<int>& dst, const char* what);
+int bs_records(const gpmdm_model* m, DevBuf<double>& rec, DevBuf<double>& mu, DevBuf<double>& var, DevBuf<double>& q,
+               const double* T, long long n_s, const double* Xs, const int* cs, const double* a, hipStream_t s);
 int iv_wait(gpmdm_pf* pf);             // an innovation call's launches in flight (capi_innov.hip)
 // gating (capi_gate.hip): the end of a gated-mode weigh on s; the log il2 table of the filter's
 // (new) model

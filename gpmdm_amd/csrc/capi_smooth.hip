@@ -23,6 +23,7 @@ int sm_wait(gpmdm_pf* pf) {
   }
   TRY(pf->bs_out.wait());
   TRY(pf->mp_out.wait());
+  TRY(pf->fs_out.wait());
   return pf->sm_out.wait();
 }
 

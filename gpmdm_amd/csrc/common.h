@@ -160,7 +160,9 @@ enum RngStream : unsigned {
   kStreamSystematic = 3,
   // the forecast roll-out's draws (forecast.h): sub = (horizon step << 8) | pair
   kStreamForecastSwitch = 4,
-  kStreamForecastDyn = 5
+  kStreamForecastDyn = 5,
+  // backward simulation's uniforms (backsample.h): index = trajectory, sub = lag
+  kStreamBackSample = 6
 };
 
 // Order-preserving uint64 image of a double (atomicMax on doubles).

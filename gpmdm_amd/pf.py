@@ -147,6 +147,27 @@ class MapPath:
     observation_mean: Optional[torch.Tensor] = None     # (n, D)
 
 
+@dataclass
+class SampledTrajectories:
+    """``GPMDM_PF.sample_trajectories``'s result; row l is lag ``lags[l]`` = l, i.e. frame ``frames[l]``.
+    ``indices[l, m]`` is trajectory m's particle in frame ``frames[l]``'s recorded cloud
+    (``export_state``'s order).  A trajectory that no particle of an older frame reaches is dead from
+    there on: index and class -1, NaN states; ``alive[l]`` counts the others, over which the row's
+    fractions, mean and pose are taken (NaN when none is left), and ``distinct[l]`` the distinct
+    particles they sit on."""
+    lags: torch.Tensor                                  # (L + 1,) int64
+    frames: torch.Tensor                                # (L + 1,) int64: frame - lag
+    indices: torch.Tensor                               # (L + 1, n) int64
+    classes: torch.Tensor                               # (L + 1, n) int64
+    states: torch.Tensor                                # (L + 1, n, d)
+    class_probabilities: torch.Tensor                   # (L + 1, C)
+    state_mean: torch.Tensor                            # (L + 1, d)
+    alive: torch.Tensor                                 # (L + 1,) int64
+    distinct: torch.Tensor                              # (L + 1,) int64
+    observation_mean: Optional[torch.Tensor] = None     # (L + 1, D)
+    observation_spread: Optional[torch.Tensor] = None   # (L + 1, D)
+
+
 def _step_arrays(model, T, Xs, cs, Xt, ct, name):
     """The arrays ``backward_step`` and ``map_step`` share, checked: (arr, T, Xs, cs, Xt, ct)."""
     d, C = int(model.d), int(model.n_classes)
@@ -193,6 +214,29 @@ def map_step(model, T, Xs, cs, Xt, ct, delta=None, ll=None):
                                           _lib.dptr(d_), n_t, _lib.dptr(Xt_), _lib.i64ptr(ct_), _lib.dptr(l_),
                                           _lib.dptr(out), _lib.i64ptr(psi), stream), "map_step")
     return torch.from_numpy(out), torch.from_numpy(psi)
+
+
+def backward_sample_step(model, T, Xs, cs, Xt, ct, u, a=None):
+    """One step of backward simulation (gpmdm_backward_sample_step): sources ``Xs`` (n_s, d), ``cs``
+    with filter weights ``a`` (None: 1 / n_s each), targets ``Xt`` (n_t, d), ``ct`` and one uniform
+    ``u[j]`` in [0, 1) per target, transition density ``backward_step``'s f.  Returns ``(indices,
+    log_den)`` as CPU tensors: ``indices[j]`` is the lowest k with ``sum_{i <= k} a_i f_ij > u_j D_j``
+    (the sources in index order), ``log_den[j] = log D_j``, ``D_j = sum_k a_k f_kj``; -1 and -inf when
+    no source reaches j.  A source of term zero is never returned.  A pure, bit-reproducible
+    function of its inputs; target j's result does not depend on the other targets."""
+    arr, Tm, Xs_, cs_, Xt_, ct_ = _step_arrays(model, T, Xs, cs, Xt, ct, "backward_sample_step")
+    n_s, n_t = Xs_.shape[0], Xt_.shape[0]
+    u_ = arr(u, (n_t,), "u")
+    if not ((u_ >= 0) & (u_ < 1)).all():
+        raise ValueError("u must lie in [0, 1)")
+    a_ = None if a is None else arr(a, (n_s,), "a")
+    idx, ld = np.zeros(n_t, dtype=np.int64), np.zeros(n_t)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(model.device).cuda_stream)
+    _lib.check(_lib.load().gpmdm_backward_sample_step(model.handle, _lib.dptr(Tm), n_s, _lib.dptr(Xs_),
+                                                      _lib.i64ptr(cs_), _lib.dptr(a_), n_t, _lib.dptr(Xt_),
+                                                      _lib.i64ptr(ct_), _lib.dptr(u_), _lib.i64ptr(idx), _lib.dptr(ld),
+                                                      stream), "backward_sample_step")
+    return torch.from_numpy(idx), torch.from_numpy(ld)
 
 
 def backward_step(model, T, Xs, cs, Xt, ct, wt, a=None):
@@ -1171,6 +1215,58 @@ class GPMDM_PF:
                 y = y[0] if isinstance(y, (tuple, list)) else y
                 om[torch.from_numpy(ok)] = y.detach().cpu().to(torch.float64)
         return MapPath(t(lags), t(self.frame - lags), t(ix), t(cl), t(st), t(sc), float(lj[0]), t(ds), t(de), t(bp), om)
+
+    def sample_trajectories(self, n, lag=None, *, seed=None, observation: bool = False) -> SampledTrajectories:
+        """``n`` draws from the joint smoothing distribution over the last ``lag`` frames' recorded
+        clouds (None: the whole recorded depth): backward simulation (FFBSi;
+        gpmdm_pf_sample_trajectories).  Trajectory m starts at a uniformly drawn particle of the
+        current cloud and steps back frame by frame, each time drawing a particle of the older
+        cloud with probability proportional to its transition density towards the one it holds
+        (``backward_sample_step`` against the filter's own proposal).  Where ``smoothed`` hangs on a
+        few ancestors, ``smoothed_marginal`` loses what ties one frame to the next and ``map_path``
+        is one sequence with no spread, these are whole class-and-state sequences that the model
+        supports -- the thing to compute the distribution of any statistic of a sequence from.
+        Cost: O(n P) per lag.  ``observation``: the pose read-out of ``current_observation`` on each
+        lag's sampled states.
+
+        The uniforms are Philox draws keyed by ``seed`` (None: the filter's own) on a stream of
+        their own, counted by (trajectory, frame, lag): trajectory m does not depend on ``n``, a
+        shorter window is a prefix of a longer one, and the same call gives the same bits.  No
+        draw is taken from the filter's streams or torch's generator and nothing in the filter
+        changes: later updates are bitwise those without the call.  Needs ``smoothing_lag`` /
+        ``set_smoothing``; single filters on one rank, ``n * P`` up to 2^36."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) < 2 ** 31:
+            raise ValueError(f"n must be an integer in [1, 2^31), got {n!r}")
+        if lag is not None and (isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or
+                                not 1 <= int(lag) <= _lib.GPMDM_SMOOTH_MAX_LAG):
+            raise ValueError(f"lag must be None or an integer in [1, {_lib.GPMDM_SMOOTH_MAX_LAG}], got {lag!r}")
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or
+                                 not 0 <= int(seed) < 2 ** 64):
+            raise ValueError(f"seed must be None or an integer in [0, 2^64), got {seed!r}")
+        if self._peers or getattr(self, "_world", 1) > 1:
+            raise ValueError("sample_trajectories serves filters on one rank, not sharded filters")
+        n, P = int(n), self._num_particles
+        if n * P > _lib.GPMDM_BACKSMOOTH_MAX_PAIRS:
+            raise ValueError(f"sample_trajectories serves up to 2^36 trajectory-particle pairs per step, got {n} x {P}")
+        if not self._smoothing_lag:
+            raise ValueError("smoothing is off: build the filter with smoothing_lag=L or call set_smoothing(L)")
+        depth = self.smoothing_depth
+        n_lag = depth if lag is None else int(lag)
+        if n_lag > depth or n_lag < 1:
+            raise ValueError(f"lag {n_lag} is outside [1, the recorded depth {depth}] (smoothing lag {self._smoothing_lag})")
+        C, d, D, L1 = self.num_classes, self.latent_dim, self.observation_dim, n_lag + 1
+        ix, cl = np.zeros((L1, n), dtype=np.int64), np.zeros((L1, n), dtype=np.int64)
+        st, cp, sm = np.zeros((L1, n, d)), np.zeros((L1, C)), np.zeros((L1, d))
+        al, ds = np.zeros(L1, dtype=np.int64), np.zeros(L1, dtype=np.int64)
+        om, os_ = (np.zeros((L1, D)), np.zeros((L1, D))) if observation else (None, None)
+        out = _lib.SampleOut(_lib.i64ptr(ix), _lib.i64ptr(cl), _lib.dptr(st), _lib.dptr(cp), _lib.dptr(sm),
+                             _lib.i64ptr(al), _lib.i64ptr(ds), _lib.dptr(om), _lib.dptr(os_))
+        key = None if seed is None else ctypes.byref(ctypes.c_uint64(int(seed)))
+        _lib.check(_lib.load().gpmdm_pf_sample_trajectories(self._h, n, n_lag, key, ctypes.byref(out), self._stream()),
+                   "sample_trajectories")
+        lags = np.arange(L1, dtype=np.int64)
+        t = lambda x: None if x is None else torch.from_numpy(x)   # noqa: E731
+        return SampledTrajectories(t(lags), t(self.frame - lags), *map(t, (ix, cl, st, cp, sm, al, ds, om, os_)))
 
     @property
     def frame(self) -> int:

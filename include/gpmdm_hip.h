@@ -850,6 +850,63 @@ int gpmdm_backward_step(gpmdm_model_t model, const double* T, int64_t n_s, const
 int gpmdm_pf_smoothed_marginal(gpmdm_pf_t pf, int lag_first, int lag_last, const gpmdm_marginal_out* out,
                                void* stream);
 
+/* Backward simulation over the history ring (FFBSi; Godsill, Doucet & West 2004): draws from the
+ * joint smoothing distribution -- whole class-and-state sequences that the model supports, many of
+ * them -- where gpmdm_pf_smoothed gives the genealogy, gpmdm_pf_smoothed_marginal per-frame
+ * marginals and gpmdm_pf_map_path one sequence.  The transition density f is gpmdm_backward_step's.
+ * gpmdm_backward_sample_step (host arrays; a pure function of its inputs): sources Xs (n_s x d), cs
+ * with filter weights a (NULL: 1 / n_s each), targets Xt (n_t x d), ct, one uniform u_j in [0, 1)
+ * per target;
+ *   D_j = sum_k a_k f_kj,            log_den_out[j] = log D_j,
+ *   idx_out[j] = the lowest k with sum_{i <= k} a_i f_ij > u_j D_j, the sources in index order;
+ * idx_out[j] = -1 and log_den_out[j] = -inf when no source reaches j (D_j = 0, or every term -inf).
+ * A source whose term is zero (a_k = 0, T[c_k, c'_j] = 0, an unusable variance) is never returned;
+ * whenever D_j > 0 a source is returned: if rounding finds no crossing, the last source of
+ * positive term that was searched.  The sums are gpmdm_backward_step's running power-of-two sums,
+ * cut into ranges of GPMDM_BACKSAMPLE_RANGE sources -- a function of n_s alone -- and combined in
+ * range order, without floating-point atomics: the same inputs give the same bits, and the result
+ * for target j depends neither on the other targets nor on n_t.  GPMDM_E_INVALID:
+ * gpmdm_backward_step's refusals (a class outside [0, C), more than 2^36 pairs, more than 1 GiB of
+ * records) or a u outside [0, 1).  idx_out and log_den_out may be NULL.
+ * gpmdm_pf_sample_trajectories(pf, n, lag, seed, out, stream): n trajectories over the window of
+ * `lag` lags behind the last completed frame t, P particles.  Trajectory m starts at
+ * j_0 = min(P - 1, floor(u_{m,0} P)) in the current cloud and for l = 0 .. lag - 1 draws j_{l+1} in
+ * frame t - l - 1's recorded cloud by one step with that cloud as sources (post-resample: every
+ * a_k = 1 / P), target j_l and uniform u_{m,l+1}.  A trajectory whose step returns -1 stays -1 for
+ * all older lags: its class is -1 and its states are NaN.  u_{m,l} = the [0, 1) uniform of the
+ * first two words of Philox4x32-10 with key `seed` (NULL: the handle's own, as gpmdm_pf_forecast)
+ * and counter (m, frame, stream 6, l): trajectory m is a function of (seed, frame, m, history)
+ * alone -- not of n, and a shorter window is a prefix of a longer one.  The call takes no draw
+ * from the filter's own streams and changes nothing in the filter (no frame or health counter, a
+ * pending pre-switch stays pending, later frames are bitwise those without the call).  Row l of
+ * each output that is not NULL is lag l, frame t - l; class_prob = class counts / alive and
+ * state_mean = the sum over the alive trajectories / alive (both NaN when alive is 0; the sums
+ * have a fixed order and are carried in two terms); distinct = the distinct particles of slot l
+ * among the alive ones; obs_mean / obs_spread = the pose read-out gpmdm_pf_smoothed runs on a
+ * traced cloud, here on the alive sampled states of lag l (NaN when alive is 0).  GPMDM_E_INVALID,
+ * decided before any launch: banks, sharded filters, smoothing off, n outside [1, 2^31), n x P above
+ * 2^36, lag outside [1, depth], more than 1 GiB of records or of staging (the uniforms, indices,
+ * classes and states of every lag); GPMDM_E_STATE between a switch and its resample.  Everything
+ * is queued on `stream` and ends with one copy-out and one wait (with a pose: the read-outs, whose
+ * sizes are the alive counts, and a second wait); the scratch lives on the handle, grown on demand. */
+#define GPMDM_BACKSAMPLE_RANGE 1024
+typedef struct gpmdm_sample_out {   /* host arrays; any may be NULL; L = lag + 1 */
+  int64_t* index;         /* L x n: j_l of every trajectory, a particle of slot l (-1: dead) */
+  int64_t* classes;       /* L x n */
+  double* states;         /* L x n x d */
+  double* class_prob;     /* L x C */
+  double* state_mean;     /* L x d */
+  int64_t* alive;         /* L */
+  int64_t* distinct;      /* L */
+  double* obs_mean;       /* L x D */
+  double* obs_spread;     /* L x D */
+} gpmdm_sample_out;
+int gpmdm_backward_sample_step(gpmdm_model_t model, const double* T, int64_t n_s, const double* Xs, const int64_t* cs,
+                               const double* a, int64_t n_t, const double* Xt, const int64_t* ct, const double* u,
+                               int64_t* idx_out, double* log_den_out, void* stream);
+int gpmdm_pf_sample_trajectories(gpmdm_pf_t pf, int64_t n, int lag, const uint64_t* seed, const gpmdm_sample_out* out,
+                                 void* stream);
+
 /* MAP trajectory decoding over the history ring: the most probable class-and-state sequence on
  * the particle grid (particle Viterbi; Godsill, Doucet & West 2001) -- one consistent trajectory
  * where gpmdm_pf_smoothed and gpmdm_pf_smoothed_marginal give per-frame marginals.  It takes no
